@@ -1,9 +1,19 @@
 #!/usr/bin/env python3
 """SP-NeRF train-step throughput on MI355X (ray-samples/s), BASELINE.json metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c5|...] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c5|...] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-secondary] [...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: set-up, warm-up (and the HIP-graph
+capture), the K timed steps, the outputs of the last timed step to ``--dump-outputs DIR`` when
+asked, and the result line.  ``--full`` adds every other leg to that line: the C2 / C5
+``secondary`` workloads, ``cpu_baseline``, the ``psnr_parity`` / ``psnr_seeds`` studies, the
+per-kernel figures that take eager steps of their own after a graph-mode timed region
+(``roofline``, ``rooflines_top3``, ``mlp_mfma_utilisation``, ``kernels``; ``--eager`` runs and
+C5 record them inside the timed steps and report them either way) and the paired replays behind
+``allreduce_exposed_paired_replays``.
 
 ``--gpus N`` without torchrun's environment starts the N ranks itself (a torch.distributed.run
 child process, launched before anything touches the GPU); under torchrun, WORLD_SIZE must
@@ -17,9 +27,9 @@ flat gradient bucket (N > 1), Adam.
 The default workload is BASELINE.json configs[3] (C4: the training workload the 1/2/4/8-GPU
 metric is quoted on — C3's README-recipe flags with the bf16 MLP at a GLOBAL batch of 4096 rays
 per step, split over the ranks: strong scaling).  At N=1 the same 4096-ray step runs on one
-GPU.  C2 (configs[1], fp32) is reported beside it as ``secondary`` at N=1.  ``roofline``
-reports the dominant kernel from HIP events recorded by the library around each of its
-launches; ``cpu_baseline`` times the repo's PyTorch-CPU oracle (the reference algorithm
+GPU.  With ``--full``: C2 (configs[1], fp32) is reported beside it as ``secondary`` at N=1;
+``roofline`` reports the dominant kernel from HIP events recorded by the library around each of
+its launches; ``cpu_baseline`` times the repo's PyTorch-CPU oracle (the reference algorithm
 restated, parity-pinned) on the host cores for a bounded sample of the workload.
 """
 from __future__ import annotations
@@ -746,6 +756,36 @@ def kernel_table(steps):
     return dict(sorted(out.items(), key=lambda kv: -kv[1]["ms_per_step"]))
 
 
+DUMP_BUDGET = 48 << 20   # bytes of --dump-outputs arrays in all
+
+
+def dump_outputs(path, tensors, budget: int = DUMP_BUDGET):
+    """``--dump-outputs``: every tensor of ``tensors`` (name -> tensor; other values are skipped)
+    as ``path/<name>.npy``, floating point as float32 (float64 stays), integers as float64.
+    The arrays together hold at most ``budget`` bytes: the small ones whole, and of each one above
+    its equal share of what is left a fixed sample — the sorted flat indices
+    ``default_rng(0).choice(numel, share)``, a function of the array's size and the set of names
+    only, so two builds of the same workload write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor):
+            continue
+        t = t.detach()
+        keep = torch.float64 if (t.dtype == torch.float64 or not t.dtype.is_floating_point) else torch.float32
+        arrs[name] = t.to(keep).cpu().numpy()
+    left, share = budget, {}
+    for k, name in enumerate(sorted(arrs, key=lambda n: arrs[n].nbytes)):   # smallest first: water-filling
+        share[name] = min(arrs[name].nbytes, left // (len(arrs) - k))
+        left -= share[name]
+    for name, v in arrs.items():
+        if share[name] < v.nbytes:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, share[name] // v.itemsize, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), v)
+
+
 def c5_shard(c, rank, world, dev, img_downscale=None):
     """Rank ``rank``'s row shard [r0, r1) of the C5 image: its RPC rays (GPU generator), synthetic
     semantic labels as a fixed function of the GLOBAL ray index (so a shard's labels do not depend
@@ -818,6 +858,8 @@ def run_inference(a, config, rank, world, dev, steps=None, warmup=None, secondar
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
+    if a.dump_outputs and rank == 0 and not secondary:
+        dump_outputs(a.dump_outputs, res)
     dom = dominant_class()
     nt = _lib.prof_read(dom)
     total = world * B * c["n_samples"] * steps
@@ -837,7 +879,7 @@ def run_inference(a, config, rank, world, dev, steps=None, warmup=None, secondar
     }
     if a.full_image and not secondary:
         out["full_image"] = full_image(rays, sems, model, args, B, rank, world, dev, h, w, c, r0)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not secondary:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not secondary:
         out["cpu_baseline"] = cpu_baseline(c, a.cpu_seconds, a.cpu_batch or 1024)
     return out
 
@@ -927,8 +969,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c4", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 line reported beside the default C4 at N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, every other leg: the C2 / C5 secondaries, the CPU baseline, the "
+                         "PSNR studies, the per-kernel / roofline figures from profiled eager steps after a graph-mode "
+                         "timed region, the paired replays of the exposed collective (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the render's outputs, the "
+                         "loss, the flat gradient and the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline and the PSNR studies")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="(--full) skip the C2 / C5 lines reported beside the default C4 at N=1")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam(fused=True) instead of spnerf_amd.optim.Adam")
     ap.add_argument("--torch-loss", action="store_true", help="the losses module (plain torch) instead of the fused loss kernels")
     ap.add_argument("--torch-gather", action="store_true", help="torch indexing per field instead of the one-launch batch gather")
@@ -1003,7 +1053,7 @@ def main():
         out = run_inference(a, a.config, rank, world, dev)
     else:
         out = run_train(a, a.config, rank, world, dev)
-    if rank == 0 and world == 1 and a.config == "c4" and not a.no_secondary:
+    if a.full and rank == 0 and world == 1 and a.config == "c4" and not a.no_secondary:
         # configs[1] (C2, fp32) and configs[4] (C5, whole-image inference: 10 of its 32768-ray
         # chunks) beside the headline, same process and GPU, no CPU leg
         keys = ("value", "unit", "ms_per_step", "dtype", "config", "roofline", "mlp_mfma_utilisation")
@@ -1318,7 +1368,9 @@ def graph_allreduce_enabled(a) -> bool:
 
 def run_train(a, config, rank, world, dev, secondary=False):
     """One training workload: warm-up, HIP-graph capture, ``a.steps`` timed steps (barrier +
-    synchronize on both sides, max over ranks), per-kernel timings; returns the JSON record."""
+    synchronize on both sides, max over ranks), the last step's outputs to ``--dump-outputs``;
+    with ``--full`` the per-kernel timings (graph mode: from eager steps of their own), the paired
+    replays, the CPU baseline and the PSNR studies; returns the JSON record."""
     ts = TrainStep(a, config, rank, world, dev, secondary=secondary)
     c, B = ts.c, ts.B
     # a step still running after SPNERF_STEP_DEADLINE seconds ends this rank with one JSON
@@ -1363,8 +1415,14 @@ def run_train(a, config, rank, world, dev, secondary=False):
     elapsed = float(elapsed.item())
     final_loss = float(loss.item())
     finite = bool(torch.isfinite(ts.res["rgb_coarse"]).all()) and math.isfinite(final_loss)
+    if a.dump_outputs and rank == 0 and not secondary:
+        # what the last timed step handed back: the render's outputs, its loss, the (reduced) flat
+        # gradient and the parameters after Adam
+        dump_outputs(a.dump_outputs, dict(ts.res, loss=loss, flat_grad=ts.model._flat_grad,
+                                          params=torch.cat([p.detach().reshape(-1) for p in ts.params])))
     prof_steps = a.steps
-    if a.graph:
+    profiled = a.full or not a.graph   # eager timed steps carry the library's events themselves
+    if a.graph and a.full:
         # library kernels inside a graph replay carry no events: time them over eager steps
         # of the same workload right after the timed region (same kernels, same shapes)
         prof_steps = max(1, a.prof_steps)
@@ -1386,16 +1444,23 @@ def run_train(a, config, rank, world, dev, secondary=False):
     allreduce_eager_ms = allreduce_ms
     # graph mode with the collectives captured: the exposed all-reduce from paired replays of the
     # graph with and without the buckets (the eager-step figure is kept beside it)
-    paired = ts.exposed_collective_ms(wd=wd) if (ts.in_graph and a.graph) else None
+    paired = ts.exposed_collective_ms(wd=wd) if (ts.in_graph and a.graph and a.full) else None
     if paired is not None:
         allreduce_ms = paired["exposed_ms"]
     wd.close()
 
-    kernels = kernel_table(prof_steps)
-    # dominant kernel = the kernel function with the most time in the profiled steps
-    dom = dominant_class()
-    nt = _lib.prof_read(dom)
-    traffic, traffic_src = measured_traffic(config, B, dom)
+    prof = {}
+    if profiled:
+        # dominant kernel = the kernel function with the most time in the profiled steps
+        dom = dominant_class()
+        nt = _lib.prof_read(dom)
+        traffic, traffic_src = measured_traffic(config, B, dom)
+        prof = {"roofline": roofline_of(dom, nt, traffic, traffic_src),
+                # the same figures for the three MLP kernel functions with the most time (the dominant
+                # one first): which kernel is "dominant" can change between trees with nearly equal times
+                "rooflines_top3": top_rooflines(config, B, 3),
+                "mlp_mfma_utilisation": gemm_totals(prof_steps),
+                "kernels": kernel_table(prof_steps)}
     total = world * B * ts.s_final * a.steps
     buckets = ts.buckets
     out = {
@@ -1414,11 +1479,7 @@ def run_train(a, config, rank, world, dev, secondary=False):
                 "(JAX_214 proxy, resident in HBM), seeded-random SPNeRF init",
         "config": {"workload": c["workload"], "global_batch": B * world, "rays_per_rank": B,
                    "samples_per_ray": ts.s_final, "parallelism": f"dp{world}"},
-        "roofline": roofline_of(dom, nt, traffic, traffic_src),
-        # the same figures for the three MLP kernel functions with the most time (the dominant one
-        # first): which kernel is "dominant" can change between trees with nearly equal times
-        "rooflines_top3": top_rooflines(config, B, 3),
-        "mlp_mfma_utilisation": gemm_totals(prof_steps),
+        **{k: v for k, v in prof.items() if k != "kernels"},
         "allreduce_ms_per_step": allreduce_ms,
         "allreduce_ms_eager_steps": allreduce_eager_ms if paired is not None else None,
         "allreduce_exposed_paired_replays": paired,
@@ -1431,12 +1492,13 @@ def run_train(a, config, rank, world, dev, secondary=False):
                       if (buckets is not None and a.graph) else
                       f"{len(buckets.buckets)} buckets behind the backward's gradient marks (exposed ms above)"
                       if buckets is not None else "one flat all-reduce after the backward"),
-        "kernels": kernels,
+        **{k: v for k, v in prof.items() if k == "kernels"},
         "final_loss": final_loss,
         "finite": finite,
         "execution": (("hip graph of render+loss+backward" + (" + the bucket all-reduces" if ts.in_graph else "")
                        + " per step, " + ("" if (ts.in_graph or world == 1) else "eager all-reduce + ")
-                       + f"fused Adam eager; kernel timings from {prof_steps} eager steps right after the timed region")
+                       + "fused Adam eager"
+                       + (f"; kernel timings from {prof_steps} eager steps right after the timed region" if a.full else ""))
                       if a.graph else "eager"),
         "random_draws": "on-device Philox keyed by (seed, step, global ray id, slot) inside the sampling / "
                         "compositing kernels (spnerf_amd.PhiloxRandom)",
@@ -1445,7 +1507,7 @@ def run_train(a, config, rank, world, dev, secondary=False):
         out["parity_note"] = PARITY_NOTE_BF16
     ts.close()
     del ts
-    if rank == 0 and world == 1 and not secondary and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not secondary and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(c, a.cpu_seconds, a.cpu_batch or min(B, 512))
         if config in ("c2", "c4"):
             if a.psnr_parity_steps > 0:

@@ -75,6 +75,42 @@ def test_synthetic_worst_case_line_fits_the_budget():
     assert "trimmed" in line
 
 
+def test_dump_outputs_whole_small_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 / float64 .npy files, small arrays whole, the
+    arrays above their share a fixed sample (same elements on every call), the total within the
+    budget, non-tensors skipped."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(5000, 7, generator=g)
+    t = {"small": torch.arange(12.0).reshape(3, 4), "labels": torch.tensor([0, 2, -100]), "half": big[:10].bfloat16(),
+         "wide": big.double(), "big": big, "note": "not a tensor", "none": None}
+    budget = 40000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), t, budget=budget)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(got) == {"small", "labels", "half", "wide", "big"}
+    assert sum(v.nbytes for v in got.values()) <= budget
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], t["small"].numpy())
+    assert got["labels"].dtype == np.float64 and got["labels"].tolist() == [0.0, 2.0, -100.0]
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], t["half"].float().numpy())
+    assert got["wide"].dtype == np.float64 and got["big"].dtype == np.float32
+    # the large arrays: a sample of their own elements, in order, at least a third of the budget each
+    for name in ("big", "wide"):
+        v, src = got[name], t[name].numpy().reshape(-1)
+        assert v.ndim == 1 and budget // 3 <= v.nbytes < src.nbytes
+        idx = np.sort(np.random.default_rng(0).choice(src.size, v.size, replace=False))
+        assert np.array_equal(v, src[idx])
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{name}.npy"))
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
 def test_compact_rounds_floats_only():
     v = {"a": 1.234567890123, "b": [3, 2.000001, float("inf")], "c": "x", "d": True, "e": 0.0, "f": 12345678}
     got = bench.compact(v)

@@ -94,7 +94,7 @@ def test_bench_default_line_carries_c5_secondary():
     line fits the parse budget and carries roofline, cpu_baseline, the study's summary and the C5
     secondary with its roofline and MLP MFMA utilisation."""
     detail = os.path.join(ROOT, "gpurun_out", "psnr_detail_test.json")
-    d = _bench("secondary", "--global-batch", "512", "--steps", "3", "--warmup", "2", "--prof-steps", "1",
+    d = _bench("secondary", "--full", "--global-batch", "512", "--steps", "3", "--warmup", "2", "--prof-steps", "1",
                "--cpu-seconds", "1", "--cpu-batch", "32", "--psnr-parity-steps", "3", "--psnr-steps", "20",
                "--psnr-seeds", "1", "--psnr-detail", detail, timeout=300)
     assert d["finite"] and d["n_gpus"] == 1 and d["allreduce"] is None
@@ -109,13 +109,38 @@ def test_bench_default_line_carries_c5_secondary():
     assert d["secondary"]["c2"]["value"] > 0
 
 
+def test_bench_plain_line_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) at a small batch: the headline fields only — no secondaries, CPU
+    baseline, PSNR legs or per-kernel figures — with --steps timed steps, and --dump-outputs
+    writes the last timed step's arrays (float32 / float64, finite, the render's rows = the batch)."""
+    d = _bench("plain", "--gpus", "1", "--global-batch", "512", "--steps", "3", "--warmup", "2",
+               "--dump-outputs", str(tmp_path))
+    assert d["finite"] and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2
+    assert d["metric"] == "ray-samples/sec (train step)" and d["unit"] == "ray-samples/s" and d["dtype"] == "bf16"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(512 * 128 * 1e3 / d["ms_per_step"], rel=1e-3)
+    for k in ("secondary", "cpu_baseline", "psnr_parity", "psnr_seeds", "roofline", "rooflines_top3",
+              "mlp_mfma_utilisation", "kernels"):
+        assert k not in d, k
+    got = {p.stem: np.load(p) for p in tmp_path.iterdir()}
+    assert {"rgb_coarse", "depth_coarse", "weights_coarse", "loss", "flat_grad", "params"} <= set(got)
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    for name, v in got.items():
+        assert v.dtype in (np.float32, np.float64), name
+    for name in ("rgb_coarse", "depth_coarse", "weights_coarse", "loss", "flat_grad", "params"):
+        assert np.isfinite(got[name]).all(), name
+    assert got["rgb_coarse"].shape == (512, 3) and got["weights_coarse"].shape[0] == 512
+    assert float(got["loss"]) == pytest.approx(d["final_loss"], rel=1e-4)
+    assert got["params"].size > 512 * 512 and np.abs(got["flat_grad"]).max() > 0
+
+
 def test_bench_line_rehearsed_collective():
     """bench.py at N=1 with --rehearse-collective: a one-rank RCCL group, the bucket all-reduces
     captured into the step graph and replayed; then the profiled eager steps (eager collectives),
     a SECOND capture without the buckets and paired replays of both graphs — round 5's faulting
     sequence, safe since the captured packed-weight buffers live with their graphs.  The exposed
     collective comes from the paired replays (a number, not null), the eager-step figure beside it."""
-    d = _bench("rehearse", "--rehearse-collective", "--no-secondary", "--global-batch", "512", "--steps", "3",
+    d = _bench("rehearse", "--full", "--rehearse-collective", "--no-secondary", "--global-batch", "512", "--steps", "3",
                "--warmup", "2", "--prof-steps", "2", "--no-cpu-baseline")
     assert d["finite"] and d["n_gpus"] == 1
     assert "inside the HIP graph" in d["allreduce"], d["allreduce"]

@@ -15,7 +15,7 @@ prof() {  # name, timeout, bench args
   cp $(find /tmp/prof_$name -name "*kernel_stats.csv" -print -quit) gpurun_out/prof/${name}_kernel_stats.csv &&
   python3 tools/trace_shapes.py $(find /tmp/prof_$name -name "*kernel_trace.csv" -print -quit) $KEYS > gpurun_out/prof/${name}_shapes.txt
 }
-prof c4 400 --no-cpu-baseline --no-secondary &&
-prof c4_512 300 --global-batch 512 --steps 30 --no-cpu-baseline --no-secondary &&
+prof c4 400 --full --no-cpu-baseline --no-secondary &&
+prof c4_512 300 --full --global-batch 512 --steps 30 --no-cpu-baseline --no-secondary &&
 prof c5 300 --config c5 --steps 10 --warmup 3 || exit 1
 echo done

@@ -275,6 +275,11 @@ int32_t spnerf_gather_rows(const int64_t* idx, int64_t n, int32_t nfields, const
  * Replaces the torch in-place add and clone of the host binding (rng.py PhiloxRandom.begin_render):
  * one launch instead of two per training step.  state and snap: device int64[2]. */
 int32_t spnerf_rng_begin(int64_t* state, int64_t* snap, void* stream);
+/* The draws of a key as tensors: out[r * n + i] = draw i of ray r in rng->slot, by the very device
+ * functions the consuming kernels call — kind 0: the uniform, 1: the normal.  n in [1, 65536] (the
+ * index field of the counter is 16 bits); n_rays = 0 is a no-op.  For tests and tools: the render
+ * path never materialises its draws. */
+int32_t spnerf_rng_fill(const spnerf_rng* rng, int32_t kind, int64_t n_rays, int32_t n, float* out, void* stream);
 
 /* ---- gradient readiness marks for data parallelism (no reference counterpart: the reference
  *      trains on one GPU, main.py:322-337).  A backward passes n_marks = layers + 2 points after

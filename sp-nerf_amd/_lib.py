@@ -100,6 +100,7 @@ SIGNATURES = {
     "spnerf_gather_rows": (c_int32, [c_void_p, c_int64, c_int32, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32),
                                      POINTER(c_void_p), c_void_p]),
     "spnerf_rng_begin": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "spnerf_rng_fill": (c_int32, [POINTER(Rng), c_int32, c_int64, c_int32, c_void_p, c_void_p]),
     "spnerf_prof_enable": (c_int32, [c_int32]),
     "spnerf_prof_reset": (c_int32, []),
     "spnerf_prof_read": (c_int32, [c_char_p, POINTER(c_int64), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),

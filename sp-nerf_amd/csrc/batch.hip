@@ -45,9 +45,33 @@ __global__ void k_rng_begin(int64_t* state, int64_t* snap) {
     snap[1] = step;
 }
 
+// draw i of ray `ray` as the consuming kernels draw it (spnerf_rng_fill): one thread per draw
+__global__ __launch_bounds__(256) void k_rng_fill(spnerf_rng rng, int kind, int64_t n_rays, int n,
+                                                  float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n_rays * n) return;
+    const int64_t ray = t / n;
+    const int i = (int)(t - ray * n);
+    out[t] = kind ? rng_normal(rng, ray, i) : rng_uniform(rng, ray, i);
+}
+
 }  // namespace spn
 
 using namespace spn;
+
+extern "C" int32_t spnerf_rng_fill(const spnerf_rng* rng, int32_t kind, int64_t n_rays, int32_t n, float* out,
+                                   void* stream) {
+    SPN_ARG(rng && rng->state && out, "rng_fill: NULL pointer");
+    SPN_ARG(kind == 0 || kind == 1, "rng_fill: kind %d is neither 0 (uniform) nor 1 (normal)", kind);
+    SPN_ARG(n >= 1 && n <= 65536 && n_rays >= 0, "rng_fill: bad sizes (n_rays=%lld, n=%d: the index field is 16 bits)",
+            (long long)n_rays, n);
+    if (n_rays == 0) return SPNERF_OK;
+    const int64_t blocks = (n_rays * n + 255) / 256;
+    SPN_ARG(n_rays < (1ll << 31) && blocks < (1ll << 31), "rng_fill: too many draws");
+    hipLaunchKernelGGL(k_rng_fill, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, *rng, kind, n_rays, n, out);
+    SPN_HIP(hipGetLastError());
+    return SPNERF_OK;
+}
 
 extern "C" int32_t spnerf_rng_begin(int64_t* state, int64_t* snap, void* stream) {
     SPN_ARG(state && snap && state != snap, "rng_begin: null or aliased state / snapshot");

@@ -176,6 +176,9 @@ def _empty_batch(models, args, rays, ts, semantics, mode, valid_depth, target_de
 
     out = render_rays(models, args, one, pick(ts, 0), pick(semantics, 0), mode, pick(valid_depth, 0),
                       pick(target_depths, 1.5), pick(target_std, 0.1), clamp_near_far=clamp_near_far)
+    src = current_random_source()
+    if getattr(src, "on_device", False):
+        src.rewind_step()   # the placeholder's step: an empty batch draws nothing, so it costs none
     return {k: v[:0] for k, v in out.items()}
 
 

@@ -104,6 +104,27 @@ class PhiloxRandom:
         if self._state is not None:
             self._state[1].fill_(int(step))
 
+    def rewind_step(self) -> None:
+        """Undo the last ``begin_render``'s advance of the step (device and host mirror): the next
+        render draws what it would have drawn without that render.  An in-place device add, so a
+        captured HIP graph rewinds on every replay; the undone render's snapshot keeps its draws."""
+        if self._state is not None:
+            self._state[1:].sub_(1)
+        self._host_step -= 1
+
+    def fill(self, kind: str, n_rays: int, n: int, slot: int = 0, device=None) -> torch.Tensor:
+        """The draws of the current render's key as a (n_rays, n) tensor (``spnerf_rng_fill``):
+        ``kind`` "rand" (uniform) or "randn" (normal), draw i of ray r in ``slot`` as the kernels
+        draw it.  Takes no slot.  Before the first render it begins one on ``device``."""
+        from . import _lib
+        if self._snap is None:
+            self.begin_render(device)
+        key = _lib.Rng(self._snap.data_ptr(), self.ray_offset, int(slot), 0)
+        out = torch.empty(n_rays, n, dtype=torch.float32, device=self._snap.device)
+        _lib.check(_lib.lib().spnerf_rng_fill(_lib.rng_ref(key), {"rand": 0, "randn": 1}[kind], n_rays, n, _lib.ptr(out),
+                                              _lib.stream_of(out)), "rng_fill")
+        return out
+
     def sync_host_step(self) -> int:
         """Re-read the host mirror of the step from the device state (a host sync).  The mirror
         only follows eager renders: replays of a captured graph advance the device step alone."""

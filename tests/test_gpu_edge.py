@@ -87,3 +87,35 @@ def test_single_ray_equals_its_row_in_a_batch(guided, ray):
     assert sorted(full) == sorted(one)
     for k in one:
         assert torch.equal(full[k][ray:ray + 1], one[k]), k
+
+
+def test_empty_batch_takes_no_philox_step():
+    """render A, an empty batch, render B under one PhiloxRandom: A and B draw what they draw
+    without the empty batch in between (its placeholder render's step is given back), bit for bit;
+    the device step and its host mirror agree afterwards."""
+    model = make_model(ModelDims(width=64, sem=True), 9, "fp32")
+    rays = _rays(33)
+    labels, kw = _inputs(rays, True)
+    empty = rays[:0].contiguous()
+    lab0, kw0 = labels[:0], {k: v[:0] for k, v in kw.items()}
+
+    def render(src, r, lab, k):
+        with torch.no_grad(), spnerf_amd.random_source(src):
+            return spnerf_amd.render_rays({"coarse": model}, _args(True), r, None, semantics=lab, mode="train", **k)
+
+    runs = []
+    for with_empty in (True, False):
+        src = spnerf_amd.PhiloxRandom(seed=5, ray_offset=40)
+        a = render(src, rays, labels, kw)
+        if with_empty:
+            e = render(src, empty, lab0, kw0)
+            assert all(v.shape[0] == 0 for v in e.values())
+        b = render(src, rays, labels, kw)
+        host = src._host_step
+        assert src.sync_host_step() == host == 1
+        runs.append((a, b))
+    (a1, b1), (a0, b0) = runs
+    assert not torch.equal(a0["z_vals_coarse"], b0["z_vals_coarse"])   # B is another step's draws
+    for k in a0:
+        assert torch.equal(a1[k], a0[k]), k
+        assert torch.equal(b1[k], b0[k]), k

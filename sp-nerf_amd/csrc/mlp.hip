@@ -17,6 +17,7 @@
 #include <cstring>
 #include <deque>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "common.h"
@@ -1221,6 +1222,8 @@ struct Ctx {
     float* out = nullptr;           // the forward's output rows (the fused trunk + heads write them)
     bool* heads_done = nullptr;     // set when the trunk launch ran the fused heads too
     bool* heads_epi_done = nullptr;  // set when the head GEMMs' epilogues wrote the narrow heads
+    // forward_window: the window's first point in the workspace and the workspace's points (-1: no window)
+    int64_t win_p0 = 0, total_P = -1;
     float* at(int64_t off) const { return ws + off; }
     const float* pk(int64_t off) const { return P + off; }
     bf16* hb(int64_t off) const { return reinterpret_cast<bf16*>(ws + off); }          // bf16 workspace buffer
@@ -1459,6 +1462,23 @@ struct SkinnyBatch {
 // trunk saves 0.9 ms per step but the weight gradients' sin staging costs 1.25 ms (31.3 vs 31.9 ms)
 int g_zsave = 0;
 
+// Layout record of a saving pass's trunk D buffers, kept per workspace (the backward picks its
+// kernels on the host, so the record lives beside the workspace, keyed by its base address): bit l
+// set = Db[l] is tile-ordered (trunk.h dtile_off).  The forward that writes a workspace's first
+// points sets it, later windows of the pass follow it, the backward reads it (never the option).
+static std::mutex g_dtile_mu;
+static std::unordered_map<const void*, int> g_dtile_rec;
+static void dtile_set(const void* ws, int mask) {
+    std::lock_guard<std::mutex> lk(g_dtile_mu);
+    if (mask) g_dtile_rec[ws] = mask;
+    else g_dtile_rec.erase(ws);
+}
+static int dtile_get(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_dtile_mu);
+    const auto it = g_dtile_rec.find(ws);
+    return it == g_dtile_rec.end() ? 0 : it->second;
+}
+
 static bool fused_trunk_on(const Ctx& c) {
     return c.d.bf && g_fused_trunk && !c.k.Wf16.empty() && c.k.Wf16[1] >= 0;
 }
@@ -1567,6 +1587,25 @@ static int32_t forward_gemms(const Ctx& c, bool save, int mode, hipStream_t s, b
                 a.wsig = c.pk(c.k.wsig);
                 a.bsig = c.pk(c.k.bsig);
                 *sig_done = true;
+            }
+            // tile-ordered D (fused_bwd >= 2) of the layers the dX chain reads (D_{L-1} feeds the ×D
+            // head GEMM: row-major), when the saving 128-point instance runs and no 64-point block
+            // straddles two windows: the window starts on a block boundary and ends on one (or ends
+            // the workspace).  A pass's later windows follow its first one's record.
+            if (save) {
+                const int64_t pb = c.win_p0, pe = c.win_p0 + P, pt = c.total_P < 0 ? P : c.total_P;
+                const bool aligned = pb % kDtileRows == 0 && (pe % kDtileRows == 0 || pe == pt);
+                int mask = 0;
+                if (pb == 0) {
+                    if (g_fused_bwd >= 2 && aligned && trunk_dtile_ok(a))
+                        for (int l = first; l < d.L - 1; ++l) mask |= 1 << l;
+                    dtile_set(c.ws, mask);
+                } else {
+                    mask = dtile_get(c.ws);
+                    SPN_ARG(mask == 0 || (aligned && trunk_dtile_ok(a) && (mask & ((1 << first) - 1)) == 0),
+                            "mlp_forward_window: the pass's D is tile-ordered (mask %x); this window cannot follow it", mask);
+                }
+                a.dtile = mask;
             }
             // algorithmic HBM bytes: the first layer's input (fp32 PE, or H_1 and the bf16 PE)
             // in; out when saving H and D of every layer, or Z of every layer and the last H
@@ -1776,6 +1815,13 @@ static int32_t mlp_forward(const Dims& d, const float* packed, const float* rays
                            d.K0 == 3 ? 0 : d.K0 / 6, d.K0, d.K0p, planes ? nullptr : c.at(c.w.X0),
                            d.bf ? c.hb(c.w.X0b) : nullptr, planes ? c.hb(c.w.X0s) : nullptr);
         SPN_HIP(hipGetLastError());
+    }
+    // the trunk D layout record of this pass (forward_gemms sets it where the fused trunk tiles D)
+    c.win_p0 = n_total < 0 ? 0 : r0 * S;
+    c.total_P = n_total < 0 ? -1 : n_total * S;
+    if (save && d.bf) {
+        if (c.win_p0 == 0) dtile_set(ws, 0);
+        else SPN_ARG(fused_trunk_on(c) || dtile_get(ws) == 0, "mlp_forward_window: the pass's D is tile-ordered; this window runs layer by layer");
     }
     bool sig_done = false;  // hsave[p·8] (σ pre-activation) written by the fused trunk
     bool heads_done = false;  // the trunk launch ran the fused heads
@@ -2075,6 +2121,7 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
             a.dZ[i - 1] = c.hb(c.w.Db[i - 1]);
         }
         a.P = P; a.L = d.L;
+        a.dtile = dtile_get(c.ws);  // as the forward wrote each layer's D
         if (tsum && d.skip > 0 && d.skip < d.L) {
             a.Rsum[0] = c.at(c.w.Rp0); a.rs_layer[0] = 0;
             a.Rsum[1] = c.at(c.w.Rp4); a.rs_layer[1] = d.skip;
@@ -2088,6 +2135,8 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
         for (int i = d.L - 1; i >= 0; --i) SPN_TRY(layer_grads(i, i == d.L - 1 ? dZ : buf(c.w.Db[i])));
         return SPNERF_OK;
     }
+    if constexpr (BF) SPN_ARG(dtile_get(c.ws) == 0, "backward: the forward saved tile-ordered D (mask %x), which the layer-by-layer "
+                                                    "dX chain cannot read (set fused_bwd before the forward)", dtile_get(c.ws));
     for (int i = d.L - 1; i >= 0; --i) {
         // dZ (buffer cur) holds dL/d(pre-activation of layer i); the side stream has it
         SPN_TRY(layer_grads(i, dZ));
@@ -2491,7 +2540,7 @@ static int* option_slot(const char* name) {
     if (n == "tn_group") return &g_tn_group;              // weight-gradient GEMMs per group launch (1: none)
     if (n == "tn_group_last") return &g_tn_group_last;    // cap of the last group (bench.py: 2 when N > 1)
     if (n == "defer_heads") return &g_defer_heads;        // the heads' weight gradients in the group launch
-    if (n == "fused_bwd") return &g_fused_bwd;            // 0: the dX chain layer by layer
+    if (n == "fused_bwd") return &g_fused_bwd;            // 0: the dX chain layer by layer; 1: row-major D; 2: tile-ordered D
     if (n == "tn_bf16_variant") return &g_tn16_variant;   // 1: 128x128 TN tiles, 2: register-staged 256x256
     if (n == "tn_bf16_k64") return &g_tn16_k64;           // 0: N = 512, K = 64 weight gradients on 128x128 tiles
     if (n == "nt_f32_variant") return &g_nt_variant;      // the fp32 (parity) NT GEMM tilings

@@ -204,7 +204,9 @@ WS ws_layout(const Dims& d, int64_t n_rays, int32_t S, int32_t flags) {
     w.X0s = d.bf ? act(P * 4 * d.K0p) : -1;
     if (save) {
         for (int i = 0; i < d.L; ++i) w.Hb.push_back(act(P * W));
-        for (int i = 0; i < d.L; ++i) w.Db.push_back(act(P * W));
+        // D rows in whole 64-point blocks: a tile-ordered D (trunk.h dtile_off) keeps a partial last
+        // block's elements at the full block's offsets
+        for (int i = 0; i < d.L; ++i) w.Db.push_back(act((P + 63) / 64 * 64 * W));
     } else {
         for (int i = 0; i < 3; ++i) w.Hb.push_back(act(P * W));
     }

@@ -55,6 +55,54 @@ __device__ __forceinline__ f32x4 raw_f32(u32x2 v) {
 }
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]); }
 
+// Tile-ordered D (option fused_bwd >= 2): D = cos(z) of a trunk layer is private to the saving
+// trunk (k_trunk_bf16<128, 2048>, the producer) and the dX chain (k_trunk_bwd_bf16, the consumer).
+// Both hold it in the same MFMA accumulator geometry: wave w owns features [64w, 64w + 64), and per
+// 32x32 accumulator (feature tile a, 32-point tile) lane (point % 32) + 32·h holds the 16 features
+// 8·gq + 4·h + e (gq, e < 4) of one point.  The [P][512] bf16 buffer keeps its size and is permuted
+// only inside each block of kDtileRows consecutive points (64 KB, the byte range of the block's
+// row-major rows, which dZ later overwrites in place): for every (w, a, 32-point tile jj) the wave's
+// 2 KB is contiguous, as two 1-KB halves q = gq / 2; in a half, lane l's 16 B (gq % 2, e: 8
+// features) sit at 16·l.  One wave-wide b128 access is then one contiguous, 1-KB-aligned KB (8
+// whole 128-B lines), and a lane's fragment is two such accesses with no cross-lane move.
+constexpr int kDtileRows = 64;
+constexpr int kDtileBlockBytes = kDtileRows * 512 * 2;
+// byte offset in a block of lane l's 16-B piece of (wave w, feature tile a, point tile jj, half q)
+__host__ __device__ constexpr int dtile_frag_off(int w, int a, int jj, int q, int l) {
+    return ((((w * 2 + a) * 2 + jj) * 2 + q) * 64 + l) * 16;
+}
+// element offset in a block of feature f (< 512) of the block's point p (< 64)
+__host__ __device__ constexpr int dtile_off(int p, int f) {
+    const int m = f & 31, gq = m >> 3, h = (m >> 2) & 1, e = m & 3;
+    return dtile_frag_off(f >> 6, (f >> 5) & 1, p >> 5, gq >> 1, (p & 31) + 32 * h) / 2 + (gq & 1) * 4 + e;
+}
+namespace dtile_check {
+// dtile_off is a bijection of [0, 64·512) onto itself
+constexpr bool bijection() {
+    bool seen[kDtileRows * 512] = {};
+    for (int p = 0; p < kDtileRows; ++p)
+        for (int f = 0; f < 512; ++f) {
+            const int o = dtile_off(p, f);
+            if (o < 0 || o >= kDtileRows * 512 || seen[o]) return false;
+            seen[o] = true;
+        }
+    return true;
+}
+// every wave-wide 16-B access (w, a, jj, q) is the 64 lanes' pieces in lane order: one contiguous
+// KB at a 1-KB boundary, i.e. whole 128-B lines; the accesses of a block tile its 64 KB
+constexpr bool whole_lines() {
+    for (int i = 0; i < 64; ++i) {
+        const int w = i >> 3, a = (i >> 2) & 1, jj = (i >> 1) & 1, q = i & 1;
+        if (dtile_frag_off(w, a, jj, q, 0) != i * 1024) return false;
+        for (int l = 0; l < 64; ++l)
+            if (dtile_frag_off(w, a, jj, q, l) != i * 1024 + 16 * l) return false;
+    }
+    return true;
+}
+static_assert(bijection(), "dtile_off: not a bijection of the block");
+static_assert(whole_lines(), "dtile_frag_off: a wave-wide access must cover whole 128-B lines");
+}  // namespace dtile_check
+
 struct TrunkArgs {
     const bf16* H1 = nullptr;
     const bf16* X0b = nullptr;
@@ -72,6 +120,9 @@ struct TrunkArgs {
     // layers >= 1 (w0 = 1): H = sin(Z), Z = the pre-activation rounded to fp16; when saving, Ds[i]
     // receives Z as fp16 (consumers recompute cos(Z) and sin(Z)) and Hs[i] may be null
     int zround = 0;
+    // bit l: Ds[l] is written tile-ordered (dtile_off) instead of row-major — only by the saving
+    // 128-point instance; the rows allocated behind Ds[l] then cover round_up(P, kDtileRows)
+    int dtile = 0;
     // layer 0 from the rays themselves (inference, option "pe_inline"): with rays set and X0 null
     // the staging computes the encoding of o + dir·z (pe_value) instead of reading X0 rows
     const float* rays = nullptr;
@@ -105,6 +156,10 @@ struct TrunkBwdArgs {
     int L = 0;
     int dbg = 0;  // g_trunk_dbg (profiling ablations, outputs invalid): 1 = no dZ copy-outs, 2 = no D loads
     int nt = 3;   // g_trunk_bwd_nt: 1 = non-temporal dZ copy-outs, 2 = non-temporal D loads (3: the default)
+    // bit l: D[l] is tile-ordered (dtile_off, as the saving trunk wrote it; its rows cover
+    // round_up(P, kDtileRows)); dZ[l] is row-major either way and may still alias D[l]: a 64-point
+    // tile reads exactly the block it later overwrites
+    int dtile = 0;
     // per-tile column sums of dZ_l for l = rs_layer[k] (-1: none) into Rsum[k][tile][512]: the
     // per-ray sums of layer 0's and the skip layer's dZ (semantic columns) from the LDS image
     // instead of a re-read of dZ (k_ray_rowsum16).  Needs P % 64 == 0; the order is tile_colsum's
@@ -225,6 +280,8 @@ int32_t trunk2_bf16(const TrunkArgs& a, hipStream_t s, bool save, double flop, d
 int32_t trunk_bwd_bf16(const TrunkBwdArgs& a, hipStream_t s, double flop, double bytes);
 extern int g_trunk_bwd_nt;    // the dX chain's non-temporal dZ stores (1) / D loads (2)
 extern int g_trunk_bwd_dreg;  // the fused dX chain stores dZ from the epilogue's registers
-extern int g_fused_bwd;  // 1 = the bf16 training backward runs its dX chain in k_trunk_bwd_bf16
+extern int g_fused_bwd;  // >= 1: the bf16 training backward runs its dX chain in k_trunk_bwd_bf16; >= 2: tile-ordered D
+// trunk_bf16 would launch the instance that writes tile-ordered D (TrunkArgs::dtile) for these arguments
+bool trunk_dtile_ok(const TrunkArgs& a);
 
 }  // namespace spn

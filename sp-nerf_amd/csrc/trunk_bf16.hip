@@ -22,12 +22,18 @@
 //    rows are copied to HBM (one row per store instruction; scattered 8-byte stores straight
 //    from the accumulator layout cost ~2x the whole layer) behind the NEXT layer's MFMAs, which
 //    read the same image.
-// Two tilings:
-//  * TMt = 128 (inference: nothing saved but the last layer's H): 148 KB of LDS, 4 B fragments
+// Tilings:
+//  * TMt = 128, inference (nothing saved but the last layer's H): 148 KB of LDS, 4 B fragments
 //    per weight fragment (32 B/clk/CU of L2 weight traffic at the MFMA peak);
-//  * TMt = 64 (training: H_i and D_i of every layer saved for the backward): the H and D images
-//    (64 KB each) both drain behind the next layer's k-loop, instead of D leaving between two
-//    barriers; twice the weight traffic per point.
+//  * TMt = 128, training (the saving instance, VAR 2048: H_i and D_i of every layer saved for the
+//    backward): H drains from the image behind the next layer's k-loop.  D = cos of the layers the
+//    dX chain reads leaves tile-ordered (trunk.h dtile_off, option fused_bwd 2) straight from the
+//    accumulators in ONE epilogue pass (epilogue_dt: sin and cos of the same r; a wave-wide 16-B
+//    store is one whole KB); row-major D (the last layer's, which a GEMM reads; fused_bwd 1; windows
+//    off a 64-point boundary) takes two passes: cos into the image, each wave copying out its own
+//    columns, then sin over it;
+//  * TMt = 64 (option trunk_tile 64, and the saved-Z ablation path): the H and D images (64 KB
+//    each) both drain behind the next layer's k-loop; twice the weight traffic per point.
 #include <algorithm>
 #include <type_traits>
 
@@ -592,13 +598,82 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
                         __builtin_amdgcn_sched_barrier(0);  // bound the live range of hoisted loads
                     }
             };
+            // Tile-ordered D (TrunkArgs::dtile, the saving 128-point instance): ONE pass.  r = (acc + b
+            // [+ row]) [· w0] · 1/2π per pair as in epilogue_pk (the same roundings), then v_sin and
+            // v_cos of the same r: sin → the image, cos (· w0 at layer 0) → HBM straight from the
+            // registers, the lane's 16 B of a half (feature groups 2q, 2q + 1) at dtile_frag_off — one
+            // wave-wide b128 store is a whole KB, so no copy_cols, no D in LDS, no permlane swap.
+            // The stores leave per (a, q, j) group as the pass proceeds; the next layer's ring was
+            // primed in the k-loop, ahead of the first of them.
+            auto epilogue_dt = [&](auto kl0, auto krb, auto klds) {
+                constexpr float w0 = decltype(kl0)::value ? 30.f : 1.f;
+                constexpr bool RB = decltype(krb)::value;  // per-ray rows (layer 0, the skip layer)
+                constexpr bool RBL = decltype(klds)::value;  // ... staged in LDS (srb)
+                const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
+                const int rows = (int)std::min<int64_t>(TMt, g.P - p0);
+                // whole blocks that hold a valid row (a partial block's rows past P land in the
+                // buffer's padding); a block wholly past P is dropped by the hardware
+                const int brows = (rows + kDtileRows - 1) / kDtileRows * kDtileRows;
+                const __amdgpu_buffer_rsrc_t dr =
+                    __builtin_amdgcn_make_buffer_rsrc(Ds + p0 * TW, 0, (gdbg & 1) ? 0 : brows * TW * 2, 0x00020000);
+                const int dbase = dtile_frag_off(w, 0, 0, 0, el);
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        f32x4 bv2[2];
+#pragma unroll
+                        for (int u = 0; u < 2; ++u)
+                            bv2[u] = *reinterpret_cast<const f32x4*>(sb + 64 * w + 32 * a + 8 * (2 * q + u) + 4 * eh);
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+                            const int row = 32 * j + er32;
+                            u32x2 cq[2];
+#pragma unroll
+                            for (int u = 0; u < 2; ++u) {
+                                const int f0 = 64 * w + 32 * a + 8 * (2 * q + u) + 4 * eh;
+                                const int o = act_off(row, f0 >> 3) + 8 * eh;
+                                const f32x4 bv = bv2[u];
+                                f32x4 rv = f32x4{0.f, 0.f, 0.f, 0.f};
+                                if constexpr (RB) {
+                                    const int ray = (int)std::min<int64_t>(p0 + row, g.P - 1) / g.S;  // P < 2^31 / 512
+                                    rv = RBL ? *reinterpret_cast<const f32x4*>(srb + (ray - ray0) * TW + f0)
+                                             : ld4(rb + (int64_t)ray * TW + f0);
+                                }
+                                float y[4], c[4];
+#pragma unroll
+                                for (int e = 0; e < 4; e += 2) {
+                                    const int ai = 4 * (2 * q + u) + e;
+                                    f32x2 v2 = f32x2{acc[a][j][ai], acc[a][j][ai + 1]} + f32x2{bv[e], bv[e + 1]};
+                                    if constexpr (RB) v2 += f32x2{rv[e], rv[e + 1]};
+                                    const f32x2 x2 = w0 == 1.f ? v2 : v2 * f32x2{w0, w0};
+                                    const f32x2 r2 = x2 * f32x2{0.15915494309189535f, 0.15915494309189535f};
+#pragma unroll
+                                    for (int t = 0; t < 2; ++t) {
+                                        y[e + t] = __builtin_amdgcn_sinf(r2[t]);
+                                        c[e + t] = w0 == 1.f ? __builtin_amdgcn_cosf(r2[t]) : w0 * __builtin_amdgcn_cosf(r2[t]);
+                                    }
+                                }
+                                *reinterpret_cast<u32x2*>(smem + o) = u32x2{pack2(y[0], y[1]), pack2(y[2], y[3])};
+                                cq[u] = u32x2{pack2(c[0], c[1]), pack2(c[2], c[3])};
+                            }
+                            const int off = (j >> 1) * kDtileBlockBytes + dtile_frag_off(0, a, j & 1, q, 0) + dbase;
+                            if (gnt & 1)  // block-uniform: glc slc, as the row-major D copy-outs
+                                __builtin_amdgcn_raw_buffer_store_b128(u32x4{cq[0][0], cq[0][1], cq[1][0], cq[1][1]}, dr, off, 0, 3);
+                            else
+                                __builtin_amdgcn_raw_buffer_store_b128(u32x4{cq[0][0], cq[0][1], cq[1][0], cq[1][1]}, dr, off, 0, 0);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);  // bound the live range of hoisted loads
+                    }
+            };
             // block-uniform choices of compile-time instances: a load behind a runtime branch would
             // be waited for with vmcnt(0) — every refill and copy-out store in flight
             auto epi = [&](auto kpass) {
                 const std::false_type F{};
                 const std::true_type T{};
                 auto ep = [&](auto l0, auto rbk, auto lds) {
-                    if constexpr (SAVING) epilogue_pk(kpass, l0, rbk, lds);
+                    if constexpr (SAVING && decltype(kpass)::value == 3) epilogue_dt(l0, rbk, lds);
+                    else if constexpr (SAVING) epilogue_pk(kpass, l0, rbk, lds);
                     else epilogue(kpass, l0, rbk, lds);
                 };
                 if (i == 0) {
@@ -729,6 +804,11 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
                 hpend = last ? nullptr : Hs;
                 dpend = last || dreg ? nullptr : Ds;
             } else {
+                bool dt = false;  // this layer's D tile-ordered, from the registers (block-uniform)
+                if constexpr (SAVING && !NOEPI) dt = Ds && ((g.dtile >> i) & 1);
+                if (dt) {
+                    epi(std::integral_constant<int, 3>{});
+                } else {
                 if (Ds) {  // block-uniform
                     epi(std::integral_constant<int, 0>{});
 #if SPN_TRUNK_DCOLS
@@ -745,6 +825,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
                     }
                 }
                 epi(std::integral_constant<int, 1>{});
+                }
                 if (last) {
                     __syncthreads();
                     if constexpr (HEADS) {  // H_L stays on chip: the heads on this image
@@ -777,8 +858,13 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
 // DREG (option trunk_bwd_dreg, off: measured slower): dZ_{i-1} also leaves straight from the epilogue's registers
 // (permlane32-joined 16-B buffer stores, as the forward's D) instead of from the image behind the
 // next layer's k-loop, which then streams only the D rows and the weights.
-template <bool DREG>
+// DT (TrunkBwdArgs::dtile != 0): layers whose D the saving trunk wrote tile-ordered (dtile_off) load
+// their fragments — two b128 loads per accumulator, whole KBs per wave — where the row-major rows
+// load, into the same registers, and the epilogue multiplies from them: no D image write / read for
+// those layers.  Layers still row-major (per the mask) take the image as before.
+template <bool DREG, bool DT = false>
 __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntiles) {
+    static_assert(!(DREG && DT), "tile-ordered D: the image-drained chain only");
     using Geo = TrunkGeo<64>;
     constexpr int TMt = 64, NJ = Geo::NJ, IMG = Geo::IMG, CPT = Geo::CPT, TPD = Geo::TPD;
     constexpr int nks = TW / 16;
@@ -885,6 +971,24 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
         auto load_d = [&](int l) {
             const int st = opaque(tid);
             if (gdbg & 2) return;
+            if constexpr (DT) {
+                // block-uniform layout of D_l; the same loads either way (no branch around them):
+                // tile-ordered, dv[(2a + j)·2 + q] is the lane's half q of accumulator (a, j), read
+                // from the whole block (a partial block's rows past P sit in the buffer's padding)
+                const bool tl = (g.dtile >> l) & 1;
+                const __amdgpu_buffer_rsrc_t rs =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(ka->D[l]) + p0 * TW, 0, (tl ? TMt : trows) * TW * 2, 0x00020000);
+                const int tbase = dtile_frag_off(w, 0, 0, 0, st & 63);
+#pragma unroll
+                for (int q = 0; q < CPT; ++q) {
+                    const int c = st + 512 * q;
+                    const int orm = (std::min(c >> 6, trows - 1) * TW + (c & 63) * 8) * 2;
+                    const int off = tl ? tbase + q * 1024 : orm;
+                    if (gnt & 2) dv[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 3);
+                    else dv[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+                }
+                return;
+            }
             const __amdgpu_buffer_rsrc_t rs = tile_rsrc(ka->D[l], p0);
 #pragma unroll
             for (int q = 0; q < CPT; ++q) {
@@ -956,7 +1060,15 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
                 // (pend nullptr on a tile's first layer: the stores are dropped, no branch around them)
                 copy_out(gdbg & 1 ? nullptr : pend, p0, (ks0 / TPD) * per, std::integral_constant<int, per>{});
             }
-            {
+            // D_{i-1} tile-ordered (block-uniform): its fragments stay in registers through the
+            // epilogue while the next layer's load into dv
+            const bool tcur = DT && ((g.dtile >> (i - 1)) & 1);
+            u32x4 dcur[DT ? CPT : 1];
+            if constexpr (DT) {
+#pragma unroll
+                for (int q = 0; q < CPT; ++q) dcur[q] = dv[q];
+            }
+            if (!tcur) {
                 const int st = opaque(tid);
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
@@ -1004,6 +1116,27 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
+            } else if (DT && tcur) {
+                // the same product and rounding, D from the lane's own fragment registers
+                const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        const int f0 = 64 * w + 32 * a + 8 * gq + 4 * eh;
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+                            const int row = 32 * j + er32;
+                            const int o = act_off(row, f0 >> 3) + 8 * eh;
+                            const u32x4 dq = dcur[DT ? (2 * a + j) * 2 + (gq >> 1) : 0];
+                            const f32x4 dm = raw_f32(u32x2{dq[(gq & 1) * 2], dq[(gq & 1) * 2 + 1]});
+                            float v[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = acc[a][j][4 * gq + e] * dm[e];
+                            *reinterpret_cast<u32x2*>(smem + o) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
             } else {
                 const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
 #pragma unroll
@@ -1040,7 +1173,9 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
     }
 }
 
-int g_fused_bwd = 1;
+// 0 = layer by layer; 1 = the fused chain over row-major D; 2 = the saving trunk writes D tile-ordered
+// (trunk.h dtile_off) in one epilogue pass and the chain reads its fragments straight into registers
+int g_fused_bwd = 2;
 // k_trunk_bwd_bf16<true>: dZ stored from the epilogue's registers — measured SLOWER (C4: dX chain
 // 5.05-5.10 -> 5.25-5.27 ms per step, C4@512 4.42 -> 4.47 ms): unlike the forward's sin/cos, the
 // x D epilogue is too short to cover the stores, which then hold up the next k-loop's refills
@@ -1068,7 +1203,13 @@ int32_t trunk_bwd_bf16(const TrunkBwdArgs& a, hipStream_t s, double flop, double
     TrunkBwdArgs ad = a;
     ad.dbg = g_trunk_dbg;
     ad.nt = g_trunk_bwd_nt;
+    SPN_ARG((a.dtile >> (a.L - 1)) == 0, "trunk_bwd_bf16: tile-ordered layers beyond the chain (mask %x)", a.dtile);
     ProfScope prof("trunk_bwd_bf16", s, flop, bytes);
+    if (ad.dtile) {
+        hipLaunchKernelGGL((k_trunk_bwd_bf16<false, true>), dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, ntiles);
+        SPN_HIP(hipGetLastError());
+        return SPNERF_OK;
+    }
 #ifdef SPN_ABLATIONS
     if (g_trunk_bwd_dreg) hipLaunchKernelGGL(k_trunk_bwd_bf16<true>, dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, ntiles);
     else
@@ -1134,6 +1275,12 @@ int32_t trunk1_heads_bf16(const TrunkArgs& a, const HeadsFusedArgs& h, const Pac
     return SPNERF_OK;
 }
 
+bool trunk_dtile_ok(const TrunkArgs& a) {
+    bool save = false;
+    for (int i = 1; i < a.L; ++i) save |= a.Ds[i] != nullptr;
+    return save && !a.zround && trunk_tile(true) == 128 && g_trunk_var == 0 && (a.X0b_out || !trunk2_supported(a, true));
+}
+
 int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes) {
     SPN_ARG(a.P >= 0 && a.S > 0, "trunk_bf16: bad sizes");
     SPN_ARG(trunk_bf16_supported(TW, a.L, a.skip, a.K0p), "trunk_bf16: unsupported shape L=%d skip=%d K0p=%d", a.L,
@@ -1147,6 +1294,7 @@ int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes)
             "trunk_bf16: inline encoding needs z, rs, and when saving the X0b output");
     if (!a.X0b_out && trunk2_supported(a, save)) return trunk2_bf16(a, s, save, flop, bytes);
     const int tm = a.zround ? 64 : trunk_tile(save);  // the 128-point tiling has no fp16-Z path
+    SPN_ARG(a.dtile == 0 || trunk_dtile_ok(a), "trunk_bf16: tile-ordered D needs the saving 128-point instance");
     SPN_ARG(!(a.X0 || a.rays) || (a.Wf[0] && trunk_l0_supported(a.K0p, save, a.zround != 0)), "trunk_bf16: layer 0 unsupported for K0p=%d",
             a.K0p);
     TrunkArgs ad = a;

@@ -2530,7 +2530,7 @@ using namespace spn;
 static int* option_slot(const char* name) {
     const std::string n(name);
     // The product library's switches (at most 15): the default kernels and their one documented
-    // alternate each (INTEGRATION.md §Kernel selection).
+    // alternate each (INTEGRATION.md §Kernel selection), and one read-back.
     if (n == "fused_trunk") return &g_fused_trunk;        // 0: layer-by-layer trunk GEMMs
     if (n == "trunk_tile") return &g_trunk_tile;          // 64 / 128-point training tiles
     if (n == "trunk_heads") return &g_trunk_heads;        // 0: inference heads in their own launch
@@ -2540,7 +2540,8 @@ static int* option_slot(const char* name) {
     if (n == "tn_group") return &g_tn_group;              // weight-gradient GEMMs per group launch (1: none)
     if (n == "tn_group_last") return &g_tn_group_last;    // cap of the last group (bench.py: 2 when N > 1)
     if (n == "defer_heads") return &g_defer_heads;        // the heads' weight gradients in the group launch
-    if (n == "fused_bwd") return &g_fused_bwd;            // 0: the dX chain layer by layer; 1: row-major D; 2: tile-ordered D
+    if (n == "fused_bwd") return &g_fused_bwd;            // 0: the dX chain layer by layer; 1: row-major D; 2: tile-ordered D; 3: and 128-point chain tiles
+    if (n == "trunk_bwd_tile") return &g_trunk_bwd_tile;  // read-back: tile sizes (64 | 128) of the dX chain launches since zeroed
     if (n == "tn_bf16_variant") return &g_tn16_variant;   // 1: 128x128 TN tiles, 2: register-staged 256x256
     if (n == "tn_bf16_k64") return &g_tn16_k64;           // 0: N = 512, K = 64 weight gradients on 128x128 tiles
     if (n == "nt_f32_variant") return &g_nt_variant;      // the fp32 (parity) NT GEMM tilings

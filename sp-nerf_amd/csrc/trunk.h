@@ -116,7 +116,7 @@ struct TrunkArgs {
     int64_t P = 0;
     int S = 1, L = 0, skip = -1, K0p = 0;
     int dbg = 0;  // set from g_trunk_dbg by trunk_bf16
-    int nt = 0;   // set from g_trunk_nt: 1 = non-temporal copy-out stores of H, 2 = of the register-D stores
+    int nt = 0;   // set from g_trunk_nt: 1 = non-temporal copy-out stores of H, 2 = of the register-D stores, 4 = temporal tile-ordered D stores
     // layers >= 1 (w0 = 1): H = sin(Z), Z = the pre-activation rounded to fp16; when saving, Ds[i]
     // receives Z as fp16 (consumers recompute cos(Z) and sin(Z)) and Hs[i] may be null
     int zround = 0;
@@ -158,9 +158,9 @@ struct TrunkBwdArgs {
     int nt = 3;   // g_trunk_bwd_nt: 1 = non-temporal dZ copy-outs, 2 = non-temporal D loads (3: the default)
     // bit l: D[l] is tile-ordered (dtile_off, as the saving trunk wrote it; its rows cover
     // round_up(P, kDtileRows)); dZ[l] is row-major either way and may still alias D[l]: a 64-point
-    // tile reads exactly the block it later overwrites
+    // tile reads exactly the block it later overwrites, a 128-point tile its two blocks
     int dtile = 0;
-    // per-tile column sums of dZ_l for l = rs_layer[k] (-1: none) into Rsum[k][tile][512]: the
+    // per-block (64 rows) column sums of dZ_l for l = rs_layer[k] (-1: none) into Rsum[k][block][512]: the
     // per-ray sums of layer 0's and the skip layer's dZ (semantic columns) from the LDS image
     // instead of a re-read of dZ (k_ray_rowsum16).  Needs P % 64 == 0; the order is tile_colsum's
     float* Rsum[2] = {nullptr, nullptr};
@@ -280,7 +280,8 @@ int32_t trunk2_bf16(const TrunkArgs& a, hipStream_t s, bool save, double flop, d
 int32_t trunk_bwd_bf16(const TrunkBwdArgs& a, hipStream_t s, double flop, double bytes);
 extern int g_trunk_bwd_nt;    // the dX chain's non-temporal dZ stores (1) / D loads (2)
 extern int g_trunk_bwd_dreg;  // the fused dX chain stores dZ from the epilogue's registers
-extern int g_fused_bwd;  // >= 1: the bf16 training backward runs its dX chain in k_trunk_bwd_bf16; >= 2: tile-ordered D
+extern int g_fused_bwd;  // >= 1: the bf16 training backward runs its dX chain in k_trunk_bwd_bf16; >= 2: tile-ordered D; 3: 128-point chain tiles
+extern int g_trunk_bwd_tile;  // read-back: tile sizes (64 | 128) of the dX chain launches since last zeroed
 // trunk_bf16 would launch the instance that writes tile-ordered D (TrunkArgs::dtile) for these arguments
 bool trunk_dtile_ok(const TrunkArgs& a);
 

@@ -658,7 +658,9 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
                                 cq[u] = u32x2{pack2(c[0], c[1]), pack2(c[2], c[3])};
                             }
                             const int off = (j >> 1) * kDtileBlockBytes + dtile_frag_off(0, a, j & 1, q, 0) + dbase;
-                            if (gnt & 1)  // block-uniform: glc slc, as the row-major D copy-outs
+                            // block-uniform: glc slc, as the row-major D copy-outs (ablation builds:
+                            // option trunk_nt bit 8 makes the tiled D stores alone temporal)
+                            if ((gnt & 1) && !(gnt & 4))
                                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{cq[0][0], cq[0][1], cq[1][0], cq[1][1]}, dr, off, 0, 3);
                             else
                                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{cq[0][0], cq[0][1], cq[1][0], cq[1][1]}, dr, off, 0, 0);
@@ -862,13 +864,26 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
 // their fragments — two b128 loads per accumulator, whole KBs per wave — where the row-major rows
 // load, into the same registers, and the epilogue multiplies from them: no D image write / read for
 // those layers.  Layers still row-major (per the mask) take the image as before.
-template <bool DREG, bool DT = false>
+// T128 (option fused_bwd 3, every layer the chain reads tile-ordered): the forward's 128-point
+// geometry — acc[2][4], TPD 4, one 128 KB dZ image, no D image, half the weight bytes from L2 per
+// point.  A tile is two adjacent 64-point blocks of D; a lane's fragment of accumulator (a, j) is
+// dtile_frag_off(w, a, j & 1, q, lane) in block j >> 1.  A layer's D is 16 b128 loads (64 registers)
+// per lane, which the k-loop has no room for beside 128 accumulators, the ring and bc / bn; it is
+// staged in two halves by feature tile.  The a = 0 half of D_{i-2} loads in the middle of layer i's
+// epilogue, into the registers its a = 0 half has just multiplied from, and rides through the next
+// k-loop; the a = 1 half loads after the k-loop into the registers bc / bn leave free, behind the
+// barrier and the a = 0 half of the epilogue.  Same k order, product and rounding as the 64-point
+// chain: dZ is bit-identical.  Column sums: one [512] per 64-row block, at block index 2·tile + b.
+template <bool DREG, bool DT = false, bool T128 = false>
 __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntiles) {
     static_assert(!(DREG && DT), "tile-ordered D: the image-drained chain only");
-    using Geo = TrunkGeo<64>;
-    constexpr int TMt = 64, NJ = Geo::NJ, IMG = Geo::IMG, CPT = Geo::CPT, TPD = Geo::TPD;
+    static_assert(!T128 || DT, "the 128-point chain reads tile-ordered D only");
+    using Geo = TrunkGeo<T128 ? 128 : 64>;
+    constexpr int TMt = T128 ? 128 : 64, NJ = Geo::NJ, IMG = Geo::IMG, CPT = Geo::CPT, TPD = Geo::TPD;
     constexpr int nks = TW / 16;
-    __shared__ __attribute__((aligned(16))) char smem[2 * IMG + 8 * TW * 4];  // + the column-sum partials
+    constexpr int DIMG = T128 ? 0 : IMG;  // the D image (64-point tiles)
+    constexpr int PART = IMG + DIMG;      // the column-sum partials
+    __shared__ __attribute__((aligned(16))) char smem[PART + 8 * TW * 4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r32 = lane & 31, h = lane >> 5;
     const int sw = r32 & 15;
     const int gnt = kTrunkAbl ? g.nt : 3;    // product: trunk_bwd_nt 3 (non-temporal D loads and dZ stores)
@@ -920,18 +935,34 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
     };
     // per-tile column sums of the image (dZ_l, complete: called after a barrier, by every thread)
     // into dst[512]; the partials sit beyond the two images
-    auto colsum = [&](float* dst) {
-        const int cl = opaque(lane);
+    // (b: the 64-row block of a 128-point tile, one [512] sum per block)
+    // (the 128-point instance has no register to keep the row addresses in across the layers:
+    // its thread index is opaque here, so they are computed where they are used)
+    auto colsum_block = [&](float* dst, int b) {
+        const int ct = T128 ? opaque(tid) : tid;
+        const int cl = T128 ? ct & 63 : opaque(lane), cw = T128 ? ct >> 6 : w;
         u32x4 rows[8];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) rows[r] = *reinterpret_cast<const u32x4*>(smem + act_off(8 * w + r, cl));
+        for (int r = 0; r < 8; ++r) rows[r] = *reinterpret_cast<const u32x4*>(smem + act_off(64 * b + 8 * cw + r, cl));
         float a[8];
         tile_colsum_part(rows, a);
-        float* part = reinterpret_cast<float*>(smem + 2 * IMG);
-        *reinterpret_cast<f32x4*>(part + w * TW + cl * 8) = f32x4{a[0], a[1], a[2], a[3]};
-        *reinterpret_cast<f32x4*>(part + w * TW + cl * 8 + 4) = f32x4{a[4], a[5], a[6], a[7]};
+        float* part = reinterpret_cast<float*>(smem + PART);
+        *reinterpret_cast<f32x4*>(part + cw * TW + cl * 8) = f32x4{a[0], a[1], a[2], a[3]};
+        *reinterpret_cast<f32x4*>(part + cw * TW + cl * 8 + 4) = f32x4{a[4], a[5], a[6], a[7]};
         __syncthreads();
-        dst[tid] = tile_colsum_final(part, tid);
+        dst[ct] = tile_colsum_final(part, ct);
+    };
+    // the sums of tile t (Rsum base): block t, or blocks 2t and (where the tile has it) 2t + 1
+    auto colsum = [&](float* base, int t) {
+        if constexpr (T128) {
+            colsum_block(base + (int64_t)(2 * t) * TW, 0);
+            if ((int64_t)t * TMt + 64 < g.P) {  // block-uniform
+                __syncthreads();  // block 0's partials are read
+                colsum_block(base + (int64_t)(2 * t + 1) * TW, 1);
+            }
+        } else {
+            colsum_block(base + (int64_t)t * TW, 0);
+        }
     };
 
     int tile = xcd_remap(blockIdx.x, gridDim.x);
@@ -968,8 +999,35 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
         // the D rows are in — the epilogue plus TPD k-steps cover that HBM latency
         u32x4 dv[CPT];
         const int trows = (int)std::min<int64_t>(TMt, g.P - p0);
+        // T128: the lane's fragments of feature tile a (dh[a][2j + q]: half q of accumulator (a, j))
+        // through a resource over the tile's D blocks — round_up(P, 64) rows are allocated, so a
+        // last tile's absent block reads as dropped, a partial block from the buffer's padding
+        u32x4 dh[T128 ? 2 : 1][T128 ? 2 * NJ : 1];
+        // (on false: an empty resource, every load dropped — no branch around the loads, which
+        // made the waits behind the join wait for them as well)
+        auto load_dh = [&](int l, auto ka_, bool on) {
+            constexpr int a = decltype(ka_)::value;
+            const int el = opaque(lane);
+            const int64_t pad = (g.P + kDtileRows - 1) / kDtileRows * kDtileRows;
+            const int drows = (gdbg & 2) || !on ? 0 : (int)std::min<int64_t>(TMt, pad - p0);
+            const __amdgpu_buffer_rsrc_t rs =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(ka->D[l]) + p0 * TW, 0, drows * TW * 2, 0x00020000);
+            const int base = dtile_frag_off(w, a, 0, 0, el);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int off = (j >> 1) * kDtileBlockBytes + dtile_frag_off(0, 0, j & 1, q, 0) + base;
+                    if (gnt & 2) dh[a][2 * j + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 3);
+                    else dh[a][2 * j + q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
+                }
+        };
         auto load_d = [&](int l) {
             const int st = opaque(tid);
+            if constexpr (T128) {
+                load_dh(l, std::integral_constant<int, 0>{}, true);
+                return;
+            }
             if (gdbg & 2) return;
             if constexpr (DT) {
                 // block-uniform layout of D_l; the same loads either way (no branch around them):
@@ -1016,7 +1074,7 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
             __syncthreads();  // the dZ_i image is complete; the D image is free
 #pragma unroll
             for (int k = 0; k < 2; ++k)
-                if (i == g.rs_layer[k]) colsum(g.Rsum[k] + tile * TW);  // block-uniform
+                if (i == g.rs_layer[k]) colsum(g.Rsum[k], tile);  // block-uniform
             const char* brow = smem + r32 * 1024;
             bf16x8 bc[NJ];
 #pragma unroll
@@ -1062,23 +1120,52 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
             }
             // D_{i-1} tile-ordered (block-uniform): its fragments stay in registers through the
             // epilogue while the next layer's load into dv
-            const bool tcur = DT && ((g.dtile >> (i - 1)) & 1);
-            u32x4 dcur[DT ? CPT : 1];
-            if constexpr (DT) {
+            const bool tcur = DT && (T128 || ((g.dtile >> (i - 1)) & 1));
+            u32x4 dcur[DT && !T128 ? CPT : 1];
+            if constexpr (DT && !T128) {
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) dcur[q] = dv[q];
             }
+            if constexpr (T128) load_dh(i - 1, std::integral_constant<int, 1>{}, true);  // D_{i-1}'s a = 1 half
             if (!tcur) {
                 const int st = opaque(tid);
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
                     const int c = st + 512 * q;
-                    *reinterpret_cast<u32x4*>(smem + IMG + act_off(c >> 6, c & 63)) = dv[q];
+                    *reinterpret_cast<u32x4*>(smem + DIMG + act_off(c >> 6, c & 63)) = dv[q];
                 }
             }
-            if (i > 1) load_d(i - 2);  // block-uniform
+            if constexpr (!T128)
+                if (i > 1) load_d(i - 2);  // block-uniform
             __syncthreads();  // every wave is done reading dZ_i; the D image is complete
-            if constexpr (DREG) {
+            if constexpr (T128) {
+                // the DT product and rounding below from the staged halves; between them the
+                // a = 0 half of D_{i-2} loads into the registers just multiplied from (layer 1: dropped)
+                const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
+                auto half = [&](auto ka_) {
+                    constexpr int a = decltype(ka_)::value;
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        const int f0 = 64 * w + 32 * a + 8 * gq + 4 * eh;
+#pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+                            const int row = 32 * j + er32;
+                            const int o = act_off(row, f0 >> 3) + 8 * eh;
+                            const u32x4 dq = dh[T128 ? a : 0][T128 ? 2 * j + (gq >> 1) : 0];
+                            const f32x4 dm = raw_f32(u32x2{dq[(gq & 1) * 2], dq[(gq & 1) * 2 + 1]});
+                            float v[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) v[e] = acc[a][j][4 * gq + e] * dm[e];
+                            *reinterpret_cast<u32x2*>(smem + o) = u32x2{pack2(v[0], v[1]), pack2(v[2], v[3])};
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                half(std::integral_constant<int, 0>{});
+                load_dh(std::max(i - 2, 0), std::integral_constant<int, 0>{}, i > 1);
+                __builtin_amdgcn_sched_barrier(0);
+                half(std::integral_constant<int, 1>{});
+            } else if constexpr (DREG) {
                 const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
                 const int rows = (int)std::min<int64_t>(TMt, g.P - p0);
                 // (dbg 1, no copy-outs: an empty range drops every store)
@@ -1164,7 +1251,7 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
         __syncthreads();  // dZ_0 is complete
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            if (g.rs_layer[k] == 0) colsum(g.Rsum[k] + tile * TW);  // block-uniform
+            if (g.rs_layer[k] == 0) colsum(g.Rsum[k], tile);  // block-uniform
         if constexpr (!DREG) {
 #pragma unroll
             for (int q0 = 0; q0 < CPT; q0 += 4) copy_out(pend, p0, q0, std::integral_constant<int, 4>{});
@@ -1174,8 +1261,13 @@ __global__ __launch_bounds__(512) void k_trunk_bwd_bf16(TrunkBwdArgs g, int ntil
 }
 
 // 0 = layer by layer; 1 = the fused chain over row-major D; 2 = the saving trunk writes D tile-ordered
-// (trunk.h dtile_off) in one epilogue pass and the chain reads its fragments straight into registers
-int g_fused_bwd = 2;
+// (trunk.h dtile_off) in one epilogue pass and the chain reads its fragments straight into registers;
+// 3 = as 2, and the chain runs 128-point tiles (k_trunk_bwd_bf16 T128) when every layer it reads is
+// tile-ordered (else the 64-point instance, as under 2)
+int g_fused_bwd = 3;
+// read-back (option trunk_bwd_tile): the points per tile of the dX chain launches since it was last
+// zeroed, or-ed (64, 128, or 192 for both)
+int g_trunk_bwd_tile = 0;
 // k_trunk_bwd_bf16<true>: dZ stored from the epilogue's registers — measured SLOWER (C4: dX chain
 // 5.05-5.10 -> 5.25-5.27 ms per step, C4@512 4.42 -> 4.47 ms): unlike the forward's sin/cos, the
 // x D epilogue is too short to cover the stores, which then hold up the next k-loop's refills
@@ -1199,12 +1291,21 @@ int32_t trunk_bwd_bf16(const TrunkBwdArgs& a, hipStream_t s, double flop, double
     for (int k = 0; k < 2; ++k)
         SPN_ARG(a.rs_layer[k] < 0 || (a.rs_layer[k] < a.L && a.Rsum[k] && a.P % 64 == 0),
                 "trunk_bwd_bf16: column sums of layer %d need a buffer and whole 64-point tiles", a.rs_layer[k]);
-    const int ntiles = cdiv(a.P, 64);
+    int ntiles = cdiv(a.P, 64);
     TrunkBwdArgs ad = a;
     ad.dbg = g_trunk_dbg;
     ad.nt = g_trunk_bwd_nt;
     SPN_ARG((a.dtile >> (a.L - 1)) == 0, "trunk_bwd_bf16: tile-ordered layers beyond the chain (mask %x)", a.dtile);
     ProfScope prof("trunk_bwd_bf16", s, flop, bytes);
+    // the 128-point instance has no row-major path: the mask must cover every layer the chain reads
+    const bool t128 = g_fused_bwd >= 3 && ad.dtile == (1 << (a.L - 1)) - 1;
+    g_trunk_bwd_tile |= t128 ? 128 : 64;
+    if (t128) {
+        ntiles = cdiv(a.P, 128);
+        hipLaunchKernelGGL((k_trunk_bwd_bf16<false, true, true>), dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, ntiles);
+        SPN_HIP(hipGetLastError());
+        return SPNERF_OK;
+    }
     if (ad.dtile) {
         hipLaunchKernelGGL((k_trunk_bwd_bf16<false, true>), dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, ntiles);
         SPN_HIP(hipGetLastError());
@@ -1300,7 +1401,8 @@ int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes)
     TrunkArgs ad = a;
     if (ad.ldz == 0) ad.ldz = ad.S;  // contiguous z rows
     ad.dbg = g_trunk_dbg;
-    ad.nt = (g_trunk_nt & 1) | ((g_trunk_nt & 4) ? 2 : 0);  // H copy-outs / register-D stores non-temporal
+    // H copy-outs / register-D stores non-temporal; 8: the tile-ordered D stores temporal
+    ad.nt = (g_trunk_nt & 1) | ((g_trunk_nt & 4) ? 2 : 0) | ((g_trunk_nt & 8) ? 4 : 0);
     const int ntiles = cdiv(a.P, tm);
     // the saving launches (training) are their own profiling class: their roofline (HBM-heavy,
     // H and D of every layer out) is not the inference launches' (MFMA-bound)

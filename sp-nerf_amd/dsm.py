@@ -9,8 +9,11 @@ render's rays, and only the DSM (a few MB) comes back to the host.  pyproj and p
 not installed here: the UTM projection is the transverse-Mercator algorithm PROJ's utm uses
 (Krüger series) and the rasteriser plyflatten's documented behaviour — both parity unpinned
 (oracle/dsm_ref.py); lat/lon/alt is pinned to the reference's own function.  The MAE follows the
-reference's no-dsmr branch (registration by the mean Z offset, utils.py:197-201); the GDAL crop
-is the array window of the ROI grid.
+reference's no-dsmr branch (registration by the mean Z offset, utils.py:197-201) by default and,
+with ``register="ncc"``, the branch the reference runs when its modules/dsmr.py imports: the
+integer shift that maximises the normalised cross correlation over a 2x pyramid, then the Z
+offset (``compute_shift`` / ``apply_shift`` / ``dsm_pointwise_diff`` below, csrc/dsm_register.hip).
+The GDAL crop is the array window of the ROI grid.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _eval_lib, _lib
 
 _ZONE_LETTERS = "CDEFGHJKLMNPQRSTUVWXX"
 
@@ -115,10 +118,170 @@ def rasterize(ena: torch.Tensor, xoff, yoff, resolution, xsize, ysize, radius=1,
     return dsm
 
 
-def dsm_mae(pred_dsm, gt_dsm) -> float:
+def dsm_mae(pred_dsm, gt_dsm, register="z") -> float:
     """The MAE of utils.compute_mae_and_save_dsm_diff on arrays already on the ground truth's
-    grid, along the reference's no-dsmr branch (utils.py:197-201: shift by the mean Z offset)."""
-    pred = np.asarray(pred_dsm, np.float64).reshape(np.asarray(gt_dsm).shape)
-    gt = np.asarray(gt_dsm, np.float64)
-    rp = pred + np.nanmean(gt - pred)
-    return float(np.nanmean(np.abs(rp - gt)))
+    grid.  ``register="z"``: the reference's no-dsmr branch (utils.py:197-201: shift by the mean Z
+    offset), on the host.  ``register="ncc"``: the branch it runs with modules/dsmr.py —
+    ``compute_shift(gt, pred, scaling=False)``, ``apply_shift``, nanmean |.| — on the device, the
+    sums coming from the fused shift-and-error kernel (one device-to-host copy)."""
+    if register == "z":
+        pred = np.asarray(pred_dsm, np.float64).reshape(np.asarray(gt_dsm).shape)
+        gt = np.asarray(gt_dsm, np.float64)
+        rp = pred + np.nanmean(gt - pred)
+        return float(np.nanmean(np.abs(rp - gt)))
+    if register != "ncc":
+        raise ValueError(f"register must be 'z' or 'ncc', got {register!r}")
+    gt, pred = _image_pair(gt_dsm, pred_dsm)
+    reg = _register(gt, pred, 5, (0, 0))
+    sums = torch.empty(_eval_lib.DSM_SUMS_DOUBLES, dtype=torch.float64, device=gt.device)
+    _apply(pred, reg=reg.device_result, ref=gt, sums=sums)
+    total, count = sums[:2].cpu().tolist()
+    return total / count if count else float("nan")
+
+
+# ---- DSM registration (modules/dsmr.py) on the device: csrc/dsm_register.hip ------------------
+
+def _image(x, device):
+    """An array, a device tensor or the path of a float TIFF -> (H, W) float64 device tensor."""
+    if isinstance(x, (str, os.PathLike)):
+        from PIL import Image
+        with Image.open(x) as im:
+            x = np.asarray(im, np.float64)
+    if isinstance(x, torch.Tensor):
+        t = x
+    else:
+        t = torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float64))).to(device)
+    _lib.require_device(t)
+    if t.dim() == 3 and 1 in (t.shape[0], t.shape[-1]):     # (1, H, W) rasters, (H, W, 1) DSMs
+        t = t.reshape(t.shape[1:] if t.shape[0] == 1 else t.shape[:2])
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"a DSM is one (H, W) image, got shape {tuple(t.shape)}")
+    return t.to(torch.float64).contiguous()
+
+
+def _image_pair(a, b):
+    dev = next((t.device for t in (a, b) if isinstance(t, torch.Tensor) and t.is_cuda), None)
+    if dev is None:
+        # CPU tensors are refused before anything looks for a device to move arrays to
+        _lib.require_device(*[t for t in (a, b) if isinstance(t, torch.Tensor)])
+        dev = torch.device("cuda", torch.cuda.current_device())
+    a, b = _image(a, dev), _image(b, dev)
+    if a.shape != b.shape:
+        raise ValueError(f"DSMs of unequal shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.device != b.device:
+        raise ValueError(f"DSMs on different devices: {a.device} and {b.device}")
+    return a, b
+
+
+def pyramid_levels(h: int, w: int) -> int:
+    """Levels of recursive_ncc's pyramid: 1 + the 2x reductions made while min(H, W) > 100."""
+    n = 1
+    while min(h, w) > 100:
+        h, w = (h + 1) // 2, (w + 1) // 2
+        n += 1
+    return n
+
+
+class Registration:
+    """Result of ``register_dsm``: reading ``dx``, ``dy``, the moments (``muu``, ``muv``, ``sigu``,
+    ``sigv``, ``xcorr``: mean_std at the shift) or ``count`` makes the one device-to-host copy.
+    ``tables`` (if asked for): device tensor (levels, (2·irange+1)² + 2), finest level first —
+    each level's correlations in scan order (y outer, x inner), then its chosen dx, dy."""
+
+    def __init__(self, device_result, tables, irange):
+        self.device_result, self.tables, self.irange = device_result, tables, irange
+        self._host = None
+
+    def __getattr__(self, name):
+        if name in ("dx", "dy", "muu", "muv", "sigu", "sigv", "xcorr", "count"):
+            if self._host is None:
+                self._host = _eval_lib.DsmShift.from_buffer_copy(self.device_result.cpu().numpy().tobytes())
+            return getattr(self._host, name)
+        raise AttributeError(name)
+
+    def transform(self, scaling=True):
+        """compute_shift's (dx, dy, a, b)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            a = float(np.float64(self.sigu) / np.float64(self.sigv)) if scaling else 1.0
+        return self.dx, self.dy, a, self.muu - self.muv * a
+
+
+def _register(u, v, irange, init, tables=False):
+    h, w = u.shape
+    L = _eval_lib.lib()
+    nbytes = L.spnerf_eval_dsm_register_workspace_bytes(h, w, int(irange))
+    if nbytes < 0:
+        _lib.check(int(nbytes), "dsm_register_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=u.device)
+    res = torch.empty(ctypes.sizeof(_eval_lib.DsmShift), dtype=torch.uint8, device=u.device)
+    tab = None
+    if tables:
+        tab = torch.empty(pyramid_levels(h, w), (2 * irange + 1) ** 2 + 2, dtype=torch.float64, device=u.device)
+    _lib.check(L.spnerf_eval_dsm_register(_lib.ptr(u), _lib.ptr(v), h, w, int(irange), int(init[0]), int(init[1]),
+                                          _lib.ptr(ws), _lib.ptr(tab), _lib.ptr(res), _lib.stream_of(u)), "dsm_register")
+    return Registration(res, tab, irange)
+
+
+def _apply(v, dx=0, dy=0, a=1.0, b=0.0, reg=None, scaling=False, ref=None, out=None, err=None, sums=None):
+    h, w = v.shape
+    _lib.check(_eval_lib.lib().spnerf_eval_dsm_apply_shift(_lib.ptr(v), h, w, _lib.ptr(reg), 1 if scaling else 0, int(dx),
+                                                           int(dy), float(a), float(b), _lib.ptr(ref), _lib.ptr(out),
+                                                           _lib.ptr(err), _lib.ptr(sums), _lib.stream_of(v)),
+               "dsm_apply_shift")
+
+
+def downsample2x(dsm):
+    """dsmr.downsample2x on one image: the next pyramid level, (ceil(H/2), ceil(W/2)).  Returns a
+    float64 array (a device tensor when given one)."""
+    v, _ = _image_pair(dsm, dsm)
+    h, w = v.shape
+    out = torch.empty((h + 1) // 2, (w + 1) // 2, dtype=torch.float64, device=v.device)
+    _lib.check(_eval_lib.lib().spnerf_eval_dsm_down2x(_lib.ptr(v), h, w, _lib.ptr(out), _lib.stream_of(v)), "dsm_down2x")
+    return out if isinstance(dsm, torch.Tensor) else out.cpu().numpy()
+
+
+def register_dsm(dsm_ref, dsm_sec, irange=5, init=(0, 0), tables=False) -> Registration:
+    """recursive_ncc + mean_std of modules/dsmr.py on the device: the shift of ``dsm_sec`` onto
+    ``dsm_ref`` and the moments there.  ``init`` is recursive_ncc's initial (dx, dy).  Nothing is
+    copied to the host until the result is read."""
+    u, v = _image_pair(dsm_ref, dsm_sec)
+    return _register(u, v, irange, init, tables)
+
+
+def compute_shift(dsm_ref, dsm_sec, scaling=True, irange=5):
+    """dsmr.compute_shift: (dx, dy, a, b) registering ``dsm_sec`` on ``dsm_ref`` — pixel (j, i) of
+    the reference meets pixel (j + dy, i + dx) of ``dsm_sec``, whose altitudes map by
+    z -> a·z + b (a = 1 unless ``scaling``).  Each image is an array, a device tensor or the path
+    of a float TIFF.  One device-to-host copy, at the end."""
+    return register_dsm(dsm_ref, dsm_sec, irange).transform(scaling)
+
+
+def apply_shift(dsm, dx=0, dy=0, a=1, b=0):
+    """dsmr.apply_shift on an image instead of a file pair: out[j, i] = a·dsm[j + dy, i + dx] + b,
+    NaN where the source pixel is out of range.  Returns a float64 array (a device tensor when
+    given one)."""
+    v, _ = _image_pair(dsm, dsm)
+    out = torch.empty_like(v)
+    _apply(v, dx, dy, a, b, out=out)
+    return out if isinstance(dsm, torch.Tensor) else out.cpu().numpy()
+
+
+def dsm_pointwise_diff(pred, gt, gt_mask=None, register="ncc"):
+    """utils.dsm_pointwise_diff on images already on the ground truth's grid: the error map
+    registered(pred) − gt as a float64 array.  Cells where ``gt_mask`` is 9 (water) are removed
+    from ``pred`` before the registration, like the reference.  ``register="ncc"`` is the
+    reference's dsmr branch (compute_shift(gt, pred, scaling=False) then apply_shift), on the
+    device without a host sync in between; ``"z"`` its mean-offset fallback."""
+    if register not in ("ncc", "z"):
+        raise ValueError(f"register must be 'z' or 'ncc', got {register!r}")
+    g, p = _image_pair(gt, pred)
+    if gt_mask is not None:
+        m, _ = _image_pair(gt_mask, g)
+        p = torch.where(m == 9, torch.full_like(p, float("nan")), p)
+    if register == "z":
+        pn, gn = p.cpu().numpy(), g.cpu().numpy()
+        return (pn + np.nanmean(gn - pn)) - gn
+    reg = _register(g, p, 5, (0, 0))
+    err = torch.empty_like(g)
+    _apply(p, reg=reg.device_result, ref=g, err=err)
+    return err.cpu().numpy()

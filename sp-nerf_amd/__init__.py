@@ -18,6 +18,8 @@ from . import dsm  # noqa: F401  (DSM extraction: satellite_scene.py:475-568 on 
 from .rng import PhiloxRandom, ReplayRandom, TorchRandom, current_random_source, random_source, set_random_source  # noqa: F401
 from .spnerf import (SPNeRF, Mapping, Siren, first_layer_sine_init, inference, inference_rays, run_mlp,  # noqa: F401
                      sine_init)
+from . import view  # noqa: F401  (whole views: image products and the validation scores on the GPU)
+from .view import render_image, view_metrics  # noqa: F401
 
 __version__ = "0.1.0"
 

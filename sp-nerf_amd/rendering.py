@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from .rng import begin_render, current_random_source, device_key
 from .spnerf import (_result, composite, guided_inference_pass, guided_main_pass, inference_rays, mlp_saves,
-                     pack_for_render)
+                     pack_for_render, run_mlp)
 
 # Training renders with guided sampling evaluate each main-pass point once (spnerf._GuidedMain):
 # False = the reference's two evaluations of the stratified points (pass 1 σ-only, then the
@@ -188,7 +188,6 @@ def render_rays(models, args, rays, ts, semantics=None, mode='test', valid_depth
     (keys suffixed ``_coarse``).  ``clamp_near_far`` (extension, device tensor of 2 floats)
     overrides the guided-sampling clamp bounds, which otherwise are the first ray's near/far
     like the reference — data-parallel ranks pass the GLOBAL batch's first ray."""
-    N_samples = args.n_samples
     if args.model != "sp-nerf":
         raise ValueError(f'model {args.model} is not valid')
     _lib.require_device(rays)
@@ -197,6 +196,29 @@ def render_rays(models, args, rays, ts, semantics=None, mode='test', valid_depth
     if B == 0:
         return _empty_batch(models, args, rays, ts, semantics, mode, valid_depth, target_depths, target_std,
                             clamp_near_far)
+    model, pk, sem, rays_t, out, z_vals, z_unsort = _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth,
+                                                                 target_depths, target_std, clamp_near_far)
+    rgb, depth, w, T, sem_l = composite(model, out, z_vals, args.noise_std)
+    result = _result(model, out, z_vals, rgb, depth, w, T, sem_l, z_unsort)
+    if args.sc_lambda > 0:                                                           # rendering.py:171-177
+        sc = inference_rays(model, args, rays, z_vals, 8, sem, rays_t, mode="sun", pack=pk)
+        result["weights_sc"] = sc["weights"]
+        result["transparency_sc"] = sc["transparency"]
+        result["sun_sc"] = sc["sun"]
+    out = {f"{k}_coarse": v for k, v in result.items()}
+    if args.n_importance > 0:
+        out = _fine(models, args, rays, ts, z_vals, out, semantics, rays_t)
+    return out
+
+
+def _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth, target_depths, target_std, clamp_near_far):
+    """The coarse main pass of a render up to its MLP rows, shared by ``render_rays`` and
+    ``view.render_image``: the stratified depths, the guided passes when ``args.guidedsample``, and
+    the main pass's rows at the final depths — everything before the compositing.  ``rays`` is a
+    non-empty contiguous fp32 device tensor.  Returns (model, weight pack, semantics or None,
+    t-embedding or None, out (B·S, number_of_outputs), z_vals (B, S), z_vals_unsort or None)."""
+    N_samples = args.n_samples
+    B = rays.shape[0]
     begin_render(rays.device)         # a keyed on-device random source starts a new step
     key, keep = device_key(rays.device)
     if key is not None:
@@ -223,25 +245,15 @@ def render_rays(models, args, rays, ts, semantics=None, mode='test', valid_depth
         t_in = rays_t if model.beta else None
         run = guided_main_pass if mlp_saves(model, t_in) else guided_inference_pass
         out, z_vals, z_unsort = run(model, rays, z_vals, sem if model.sem else None, t_in, guide, pk)
-        rgb, depth, w, T, sem_l = composite(model, out, z_vals, args.noise_std)
-        result = _result(model, out, z_vals, rgb, depth, w, T, sem_l, z_unsort)
-    elif args.guidedsample:
+        return model, pk, sem, rays_t, out, z_vals, z_unsort
+    z_unsort = None
+    if args.guidedsample:
         with torch.no_grad():   # pass 1 feeds only the detached guided depths (rendering.py:164)
             res1 = inference_rays(model, args, rays, z_vals, 3, sem, rays_t, mode="sigma", pack=pk)
         cnf = None if clamp_near_far is None else clamp_near_far.reshape(2).to(rays.device, torch.float32).contiguous()
         z_vals, z_unsort = _guided(res1, z_vals, N_samples, rays, mode, valid_depth, target_depths, target_std, cnf)
-        result = inference_rays(model, args, rays, z_vals, 3, sem, rays_t, z_vals_unsort=z_unsort, pack=pk)
-    else:
-        result = inference_rays(model, args, rays, z_vals, 3, sem, rays_t, pack=pk)
-    if args.sc_lambda > 0:                                                           # rendering.py:171-177
-        sc = inference_rays(model, args, rays, z_vals, 8, sem, rays_t, mode="sun", pack=pk)
-        result["weights_sc"] = sc["weights"]
-        result["transparency_sc"] = sc["transparency"]
-        result["sun_sc"] = sc["sun"]
-    out = {f"{k}_coarse": v for k, v in result.items()}
-    if args.n_importance > 0:
-        out = _fine(models, args, rays, ts, z_vals, out, semantics, rays_t)
-    return out
+    out = run_mlp(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
+    return model, pk, sem, rays_t, out, z_vals, z_unsort
 
 
 def sort_rows(x: torch.Tensor) -> torch.Tensor:
@@ -254,14 +266,15 @@ def sort_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _fine(models, args, rays, ts, z_vals, result_, semantics, rays_t_coarse):
-    """Hierarchical fine pass, rendering.py:186-216, reproduced as the reference returns it:
-    with the solar pass on, ``result_`` is replaced by the fine solar inference's dictionary
-    (:207), so the coarse keys are dropped and un-suffixed fine-solar keys appear."""
+def _fine_rows(models, args, rays, ts, z_vals, weights_coarse, semantics):
+    """The fine pass up to its MLP rows (rendering.py:186-203), shared by ``_fine`` and
+    ``view.render_image``: the importance depths drawn from the coarse weights, merged and sorted,
+    and the fine model's rows there.  Returns (model, weight pack, semantics or None, t-embedding
+    or None, out, z_vals)."""
     n_imp = args.n_importance
     with torch.no_grad():
         mid = 0.5 * (z_vals[:, :-1] + z_vals[:, 1:])                               # :188
-        z_ = sample_pdf(mid, result_["weights_coarse"][:, 1:-1], n_imp, det=False)  # :189 (perturb = 1)
+        z_ = sample_pdf(mid, weights_coarse[:, 1:-1], n_imp, det=False)             # :189 (perturb = 1)
         z_vals = sort_rows(torch.cat([z_vals, z_], -1))                             # :190
     model = models["fine"]
     rays_t = None
@@ -269,7 +282,17 @@ def _fine(models, args, rays, ts, z_vals, result_, semantics, rays_t_coarse):
         rays_t = models['t'](ts) if ts else None                                    # :201, as written there
     sem = semantics if model.sem else None
     pk = pack_for_render(model)
-    result = inference_rays(model, args, rays, z_vals, 3, sem, rays_t, pack=pk)
+    out = run_mlp(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
+    return model, pk, sem, rays_t, out, z_vals
+
+
+def _fine(models, args, rays, ts, z_vals, result_, semantics, rays_t_coarse):
+    """Hierarchical fine pass, rendering.py:186-216, reproduced as the reference returns it:
+    with the solar pass on, ``result_`` is replaced by the fine solar inference's dictionary
+    (:207), so the coarse keys are dropped and un-suffixed fine-solar keys appear."""
+    model, pk, sem, rays_t, out, z_vals = _fine_rows(models, args, rays, ts, z_vals, result_["weights_coarse"], semantics)
+    rgb, depth, w, T, sem_l = composite(model, out, z_vals, args.noise_std)
+    result = _result(model, out, z_vals, rgb, depth, w, T, sem_l)
     if args.sc_lambda > 0:
         result_ = inference_rays(model, args, rays, z_vals, 8, sem, rays_t, pack=pk)  # :207 overwrites result_
         result["weights_sc"] = result_["weights"]

@@ -20,6 +20,8 @@ from .spnerf import (SPNeRF, Mapping, Siren, first_layer_sine_init, inference, i
                      sine_init)
 from . import view  # noqa: F401  (whole views: image products and the validation scores on the GPU)
 from .view import render_image, view_metrics  # noqa: F401
+from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
+from .image import ssim  # noqa: F401
 
 __version__ = "0.1.0"
 

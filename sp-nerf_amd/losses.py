@@ -174,6 +174,9 @@ def psnr(image_pred, image_gt, valid_mask=None, reduction="mean"):
     return -10 * torch.log10(mse(image_pred, image_gt, valid_mask, reduction))
 
 
+from .image import ssim  # noqa: E402,F401  (metrics.py:210-215, evaluated in fp64 by csrc/ssim.hip)
+
+
 # ------------------------------------------------------------------------------------------
 # fused training loss (csrc/loss.hip)
 # ------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib, _view_lib
+from . import _image_lib, _lib, _view_lib, image
 from .rendering import _coarse_rows, _fine_rows
 from .rng import current_random_source, device_key
 from .spnerf import composite, max_points_per_call
@@ -149,7 +149,8 @@ def render_image(models, args, rays, ts=None, semantics=None, *, chunk=None,
     return res
 
 
-def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_classes=0) -> dict:
+def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_classes=0, hw=None, ssim_layout="hwc",
+                 window_size=3) -> dict:
     """The scores the validation step logs, of a rendered view against its targets, in one pass on
     the device and one device-to-host copy: ``mse``, ``psnr`` (metrics.py:197-207, summed in fp64)
     and — with ``labels`` (int64, any label outside [0, num_classes) ignored, −100 included) and
@@ -157,7 +158,14 @@ def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_cla
     num_classes) ``confusion`` table [label, prediction], ignored labels in the last row.
     ``planes_or_rgb`` is the rgb image or ``render_image``'s dictionary (its ``sem_class`` is then
     the default).  The IoUs follow the reference's float32 arithmetic: a class whose union is 0
-    contributes 0 to the mean, and ``oa`` divides by the number of labels, ignored ones included."""
+    contributes 0 to the mean, and ``oa`` divides by the number of labels, ignored ones included.
+
+    With ``hw=(H, W)`` the view is also scored as an H x W image: ``ssim`` (metrics.py:210-215 with
+    ``window_size``, evaluated in fp64: ``spnerf_amd.ssim``) and ``ssim_channels``, its mean per
+    channel, on the same stream and in the same copy.  ``ssim_layout="hwc"`` reads the (H·W, 3)
+    buffers as the interleaved image they are (eval.py:393); ``"chw"`` reads them as three H x W
+    planes, which is what main.py:261's ``.view(1, 3, H, W)`` scores.  Without ``hw`` the result has
+    neither key."""
     if isinstance(planes_or_rgb, dict):
         rgb = planes_or_rgb["rgb"]
         if sem_class is None and labels is not None:
@@ -181,20 +189,34 @@ def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_cla
         labels = labels.reshape(-1).to(torch.int64).contiguous()
         if sem_class.numel() != n or labels.numel() != n:
             raise ValueError(f"sem_class and labels must have one entry per ray ({n})")
+    if hw is not None:
+        H, W = int(hw[0]), int(hw[1])
+        if H * W != n:
+            raise ValueError(f"hw {tuple(hw)} is not the view's {n} rays")
+        if ssim_layout not in ("hwc", "chw"):
+            raise ValueError(f"ssim_layout {ssim_layout!r} is neither 'hwc' nor 'chw'")
     L = _view_lib.lib()
     nbytes = L.spnerf_view_metrics_workspace_bytes(n, C)
     if nbytes < 0:
         _lib.check(int(nbytes), "view_metrics_workspace_bytes")
     ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=rgb.device)
-    res = torch.zeros(ctypes.sizeof(_view_lib.ViewMetricsResult), dtype=torch.uint8, device=rgb.device)
+    vm_bytes = ctypes.sizeof(_view_lib.ViewMetricsResult)      # both result structs in one buffer: one copy
+    res = torch.zeros(vm_bytes + (image.RESULT_BYTES if hw is not None else 0), dtype=torch.uint8, device=rgb.device)
     _lib.check(L.spnerf_view_metrics(n, _lib.ptr(rgb), _lib.ptr(tgt), _lib.ptr(sem_class if scored else None),
                                      _lib.ptr(labels if scored else None), C, _lib.ptr(ws), _lib.ptr(res),
                                      _lib.stream_of(rgb)), "view_metrics")
-    host = _view_lib.ViewMetricsResult.from_buffer_copy(res.cpu().numpy().tobytes())   # the one copy
+    if hw is not None:
+        image.launch_ssim(rgb, tgt, 3, H, W, (1, 3 * W, 3) if ssim_layout == "hwc" else (H * W, W, 1), window_size, 1.0,
+                          res.data_ptr() + vm_bytes)
+    raw = res.cpu().numpy().tobytes()                          # the one copy
+    host = _view_lib.ViewMetricsResult.from_buffer_copy(raw)
     result = {"mse": host.mse, "psnr": host.psnr, "n": host.n, "miou": None, "oa": None, "correct": None, "confusion": None}
     if scored:
         table = np.array(host.table[:(C + 1) * C], np.int64).reshape(C + 1, C)
         result.update(confusion=table, correct=int(host.correct), **scores_from_table(table, n))
+    if hw is not None:
+        sr = _image_lib.SsimResult.from_buffer_copy(raw, vm_bytes)
+        result.update(ssim=sr.ssim, ssim_channels=[sr.channel_mean[c] for c in range(3)])
     return result
 
 

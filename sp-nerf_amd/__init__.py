@@ -22,6 +22,8 @@ from . import view  # noqa: F401  (whole views: image products and the validatio
 from .view import render_image, view_metrics  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
+from . import losses  # noqa: F401  (modules/metrics.py, and the fused training losses)
+from .losses import FusedRenderLoss, FusedTrainLoss  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -286,3 +286,224 @@ class FusedRenderLoss(torch.nn.Module):
         loss, terms = _RenderLoss.apply(rgb.contiguous(), sun, depth, logits, cfg)
         names = ("coarse_color", "coarse_sc_term2", "coarse_sc_term3", "coarse_ds", "coarse_ss")
         return loss, {n: terms[i] for i, n in enumerate(names)}
+
+
+# ------------------------------------------------------------------------------------------
+# fused training loss, every form the trainer combines (csrc/train_loss.hip)
+# ------------------------------------------------------------------------------------------
+
+# the differentiable inputs of a pass, in the order _TrainLoss takes them (then beta_coarse)
+_PASS_INPUTS = ("rgb", "sun_sc", "depth", "sem_logits", "weights")
+_PASS_GRADS = ("d_rgb", "d_sun", "d_depth", "d_logits", "d_weights")
+
+
+class _TrainLoss(torch.autograd.Function):
+    """(cfg, 5 tensors of the coarse pass, 5 of the fine pass, beta_coarse): a slot holds a tensor
+    exactly when the configuration sends a gradient there, None otherwise."""
+
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        from . import _lib, _loss_lib
+        L = _loss_lib.lib()
+        opts, passes = cfg["opts"], cfg["passes"]
+        dev = cfg["device"]
+        ws = torch.empty(max(1, L.spnerf_train_loss_workspace_bytes(opts.n_rays) // 4), dtype=torch.float32, device=dev)
+        out = torch.empty(_loss_lib.RESULT_FLOATS, dtype=torch.float32, device=dev)
+        fine = ctypes.byref(passes[1]) if len(passes) > 1 else None
+        _lib.check(L.spnerf_train_loss_forward(ctypes.byref(opts), ctypes.byref(passes[0]), fine, _lib.ptr(ws),
+                                               _lib.ptr(out), _lib.stream_of(out)), "train_loss_forward")
+        ctx.cfg = cfg
+        ctx.present = [t is not None for t in tensors]
+        ctx.save_for_backward(out, *[t for t in tensors if t is not None])
+        terms = out[_loss_lib.PASS_BASE:]
+        ctx.mark_non_differentiable(terms)
+        # the terms take no gradient: not materialised as zeros (one fill launch per step)
+        ctx.set_materialize_grads(False)
+        return out[0], terms
+
+    @staticmethod
+    def backward(ctx, g_loss, g_terms):
+        from . import _lib, _loss_lib
+        n = len(ctx.present)
+        if g_loss is None:
+            return (None,) * (n + 1)
+        out, *rest = ctx.saved_tensors
+        rest = iter(rest)
+        tensors = [next(rest) if p else None for p in ctx.present]
+        grads = [None if t is None else torch.empty(t.shape, dtype=torch.float32, device=t.device) for t in tensors]
+        cfg = ctx.cfg
+        opts, passes = cfg["opts"], cfg["passes"]
+        k = len(_PASS_INPUTS)
+        for p, ps in enumerate(passes):
+            for j, name in enumerate(_PASS_GRADS):
+                g = grads[p * k + j]
+                setattr(ps, name, None if g is None else g.data_ptr())
+        opts.d_beta = None if grads[2 * k] is None else grads[2 * k].data_ptr()
+        g = g_loss.contiguous().float().reshape(1)
+        fine = ctypes.byref(passes[1]) if len(passes) > 1 else None
+        _lib.check(_loss_lib.lib().spnerf_train_loss_backward(ctypes.byref(opts), ctypes.byref(passes[0]), fine,
+                                                              _lib.ptr(out), _lib.ptr(g), _lib.stream_of(out)),
+                   "train_loss_backward")
+        return (None, *grads)
+
+
+def _column(t, S):
+    """A (B, S, 1) or (B, S) column as the kernels read it: element (r, s) at (r·S + s)·ld of the
+    pointer.  A strided view of the MLP output (``out.view(B, S, NO)[..., c:c+1]``, as a render
+    returns ``sun_sc`` and ``beta``) already is one and is not copied."""
+    t = t.float()
+    if t.stride(1) != t.stride(0) // S or t.stride(0) % S or t.stride(1) <= 0:
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+class FusedTrainLoss(torch.nn.Module):
+    """Every loss form the reference trainer combines (main.py:125-174) in two launches forward
+    and one backward (csrc/train_loss.hip, include/spnerf_amd_loss.h), on the coarse keys and, when
+    the render carries them, the ``*_fine`` keys:
+
+    * colour: ``SNerfLoss``, or with ``beta=True`` ``SatNerfLoss`` (uncertainty-weighted colour +
+      log β; ``beta_coarse`` weights either pass, as in the reference, so the two passes must then
+      have equal sample counts);
+    * the solar-correction terms when ``lambda_sc > 0``;
+    * ``DepthLoss(lambda_ds, GNLL, usealldepth)`` when ``lambda_ds > 0``: subset MSE, subset
+      Gaussian NLL (gradients also into ``weights_*``) or use-all-depth; ``target_depths`` is the
+      (B, 2) tensor of the dataset (depth, weight);
+    * ``SemanticLoss(lambda_ss)`` when ``lambda_ss > 0`` (``labels_global`` / ``world`` as in
+      ``FusedRenderLoss``).
+
+    Per call: ``use_beta=False`` selects the plain colour form for a β model (the first two epochs,
+    main.py:150-153); ``add_depth=False`` / ``add_sem=False`` still report the term but neither add
+    it to the loss nor differentiate it (``ds_drop`` / ``ss_drop``, main.py:163,172).
+
+    Returns ``(loss, terms)``; ``terms`` holds the reference's keys (``{typ}_color``,
+    ``{typ}_logbeta``, ``{typ}_sc_term2``, ``{typ}_sc_term3``, ``{typ}_ds``, ``{typ}_ss``) plus
+    ``mse_{typ}`` and ``psnr_{typ}`` (train/psnr, main.py:179-181), all 0-d device tensors without
+    gradient.  Gradients go to ``rgb_*``, ``sun_sc_*``, ``depth_*``, ``sem_logits_*`` and, for the
+    β and GNLL forms, to ``weights_*`` and ``beta_coarse``; no zero gradient is materialised."""
+
+    def __init__(self, lambda_sc=0.05, beta=False, lambda_ds=0.0, GNLL=False, usealldepth=False, lambda_ss=0.0):
+        super().__init__()
+        self.lambda_sc, self.lambda_ds, self.lambda_ss = float(lambda_sc), float(lambda_ds), float(lambda_ss)
+        self.beta, self.GNLL, self.usealldepth = bool(beta), bool(GNLL), bool(usealldepth)
+
+    def forward(self, inputs, targets, target_depths=None, target_valid_depth=None, target_std=None, semantics=None, *,
+                use_beta=True, add_depth=True, add_sem=True, labels_global=None, world=1):
+        from . import _lib, _loss_lib as LL
+        rgb0 = inputs["rgb_coarse"]
+        _lib.require_device(rgb0)
+        B, dev = rgb0.shape[0], rgb0.device
+        if B == 0:
+            raise ValueError("FusedTrainLoss: empty batch")
+        f32 = lambda t: t.detach().contiguous().float()   # noqa: E731  (a constant of the loss)
+        beta_on = self.beta and bool(use_beta)
+        solar, sem = self.lambda_sc > 0, self.lambda_ss > 0
+        form = LL.DEPTH_NONE
+        if self.lambda_ds > 0:
+            form = LL.DEPTH_ALL if self.usealldepth else (LL.DEPTH_SUBSET_GNLL if self.GNLL else LL.DEPTH_SUBSET_MSE)
+        subset = form in (LL.DEPTH_SUBSET_MSE, LL.DEPTH_SUBSET_GNLL)
+        g_depth, g_sem = form != LL.DEPTH_NONE and bool(add_depth), sem and bool(add_sem)
+        g_weights = beta_on or (g_depth and form == LL.DEPTH_SUBSET_GNLL)
+        keep = []   # every tensor a struct points to stays bound until the backward has run
+
+        def hold(t):
+            keep.append(t)
+            return t.data_ptr()
+
+        opts = LL.TrainLossOpts()
+        opts.n_rays, opts.world = B, int(world)
+        opts.flags = ((LL.LOSS_BETA if beta_on else 0) | (0 if add_depth else LL.LOSS_DEPTH_TERM_ONLY)
+                      | (0 if add_sem else LL.LOSS_SEM_TERM_ONLY))
+        opts.depth_form = form
+        opts.lambda_sc, opts.lambda_ds, opts.lambda_ss = self.lambda_sc, self.lambda_ds, self.lambda_ss
+        opts.ld_beta, opts.ld_td = 1, 2
+        opts.target = hold(f32(targets))
+        if form != LL.DEPTH_NONE:
+            td = target_depths.detach().float()
+            if td.dim() != 2 or td.shape[1] < 2:
+                raise ValueError(f"FusedTrainLoss: target_depths is (B, 2) (depth, weight), got {tuple(td.shape)}")
+            if td.stride(1) != 1:
+                td = td.contiguous()
+            opts.target_depth, opts.target_weight, opts.ld_td = hold(td), hold(td[:, 1:]), td.stride(0)
+            if subset:
+                if target_valid_depth is None:   # metrics.py:83-86: every ray has a prior
+                    target_valid_depth = torch.ones(B, dtype=torch.int64, device=dev)
+                opts.valid = hold(target_valid_depth.reshape(-1).long().contiguous())
+                opts.target_std = hold(f32(target_std.reshape(-1)))
+        if sem:
+            labels = semantics.reshape(-1).long().contiguous()
+            lg = labels if labels_global is None else labels_global.reshape(-1).long().contiguous()
+            opts.labels, opts.labels_global, opts.n_global = hold(labels), hold(lg), lg.numel()
+        passes, slots, counts = [], [], []
+        for typ in ("coarse", "fine"):
+            if typ == "fine" and "rgb_fine" not in inputs:
+                break
+            ps = LL.TrainLossPass()
+            ps.n_samples, ps.ld_sun = 1, 1
+            slot = dict.fromkeys(_PASS_INPUTS)
+            slot["rgb"] = inputs[f"rgb_{typ}"].contiguous().float()
+            ps.rgb = hold(slot["rgb"])
+            S = None
+
+            def samples(name, t):
+                nonlocal S
+                if S is None:
+                    S = t.shape[1]
+                elif t.shape[1] != S:
+                    raise ValueError(f"FusedTrainLoss: {name}_{typ} has {t.shape[1]} samples per ray, expected {S}")
+
+            if beta_on or subset:
+                w = inputs[f"weights_{typ}"]
+                samples("weights", w)
+                w = w.contiguous().float() if g_weights else f32(w)
+                ps.weights = hold(w)
+                if g_weights:
+                    slot["weights"] = w
+            if subset:
+                z = f32(inputs[f"z_vals_{typ}"])
+                samples("z_vals", z)
+                ps.z_vals = hold(z)
+            if form != LL.DEPTH_NONE:
+                d = inputs[f"depth_{typ}"].contiguous().float()
+                ps.depth = hold(d)
+                if g_depth:
+                    slot["depth"] = d
+            if solar:
+                sun = inputs[f"sun_sc_{typ}"]
+                samples("sun_sc", sun)
+                sun, ps.ld_sun = _column(sun, S)
+                ps.sun_sc = hold(sun)
+                slot["sun_sc"] = sun
+                ps.transparency_sc = hold(f32(inputs[f"transparency_sc_{typ}"]))
+                ps.weights_sc = hold(f32(inputs[f"weights_sc_{typ}"]))
+            if sem:
+                lo = inputs[f"sem_logits_{typ}"].contiguous().float()
+                opts.n_classes = lo.shape[1]
+                ps.sem_logits = hold(lo)
+                if g_sem:
+                    slot["sem_logits"] = lo
+            ps.n_samples = S or 1
+            counts.append(S)
+            passes.append(ps)
+            slots += [slot[k] for k in _PASS_INPUTS]
+        if len(passes) == 1:
+            slots += [None] * len(_PASS_INPUTS)
+        beta = None
+        if beta_on:
+            beta = inputs["beta_coarse"]
+            if beta.shape[1] != counts[0] or (len(counts) > 1 and counts[1] != counts[0]):
+                raise ValueError("FusedTrainLoss: the β form weights either pass's colour by beta_coarse; sample counts "
+                                 f"beta_coarse {beta.shape[1]}, weights {counts}")
+            beta, opts.ld_beta = _column(beta, counts[0])
+            opts.beta = hold(beta)
+        cfg = dict(opts=opts, passes=passes, keep=keep, device=dev)
+        loss, block = _TrainLoss.apply(cfg, *slots, beta)
+        terms = {}
+        for p, typ in enumerate(("coarse", "fine")[:len(passes)]):
+            names = ["color"] + (["logbeta"] if beta_on else []) + (["sc_term2", "sc_term3"] if solar else []) \
+                + (["ds"] if form != LL.DEPTH_NONE else []) + (["ss"] if sem else [])
+            for nm in names:
+                terms[f"{typ}_{nm}"] = block[p * LL.PASS_TERMS + LL.TERM_SLOTS[nm]]
+            for nm in ("mse", "psnr"):
+                terms[f"{nm}_{typ}"] = block[p * LL.PASS_TERMS + LL.TERM_SLOTS[nm]]
+        return loss, terms

@@ -24,6 +24,7 @@ from . import image  # noqa: F401  (image scores: the reference's metrics.ssim i
 from .image import ssim  # noqa: F401
 from . import losses  # noqa: F401  (modules/metrics.py, and the fused training losses)
 from .losses import FusedRenderLoss, FusedTrainLoss  # noqa: F401
+from . import dataset  # noqa: F401  (depth priors, semantic labels and scene.loc: satellite_scene.py on the GPU)
 
 __version__ = "0.1.0"
 

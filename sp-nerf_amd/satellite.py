@@ -81,8 +81,21 @@ def _launch(rpc: RPCModel, min_alt, max_alt, out, stride, rect=None, pixels=None
 
 
 def get_rays(cols, rows, rpc: RPCModel, min_alt, max_alt, device="cuda") -> torch.Tensor:
-    """satellite_scene.py:21-68: (n, 8) float32 [o (ECEF), d, near = 0, far = ‖far − near‖]."""
-    pix = torch.as_tensor(np.stack([np.asarray(cols), np.asarray(rows)], 1).astype(np.int32), device=device).contiguous()
+    """satellite_scene.py:21-68: (n, 8) float32 [o (ECEF), d, near = 0, far = ‖far − near‖].
+    Integer ``cols`` / ``rows`` go to the kernel as an int32 pixel list; floating-point ones
+    (fractional pixels, e.g. keypoints / img_downscale) as doubles (``spnerf_rpc_rays_f64``), which
+    gives the same bits at whole pixels."""
+    cols, rows = np.asarray(cols), np.asarray(rows)
+    if np.issubdtype(cols.dtype, np.floating) or np.issubdtype(rows.dtype, np.floating):
+        from . import _data_lib
+        pix = torch.as_tensor(np.stack([cols, rows], 1).astype(np.float64), device=device).contiguous()
+        out = torch.empty(pix.shape[0], 8, device=device)
+        _lib.require_device(out)
+        _lib.check(_data_lib.lib().spnerf_rpc_rays_f64(rpc.packed(), 1.0, float(min_alt), float(max_alt), _lib.ptr(pix),
+                                                       pix.shape[0], None, 1.0, None, _lib.ptr(out), 8,
+                                                       _lib.stream_of(out)), "rpc_rays_f64")
+        return out
+    pix = torch.as_tensor(np.stack([cols, rows], 1).astype(np.int32), device=device).contiguous()
     out = torch.empty(pix.shape[0], 8, device=device)
     _lib.require_device(out)
     _launch(rpc, min_alt, max_alt, out, 8, pixels=pix)

@@ -1,0 +1,165 @@
+"""The training-set C ABI (include/spnerf_amd_data.h, spnerf_amd._data_lib) and the host side of
+spnerf_amd.dataset: the header, the ctypes table and the built library agree, argument errors
+come back as codes or ValueErrors before anything touches the GPU — no GPU needed."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from spnerf_amd import _data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _view_lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "spnerf_amd_data.h")
+ONE = 256   # a non-NULL pointer value that is never dereferenced: the arguments are refused first
+
+
+def declarations():
+    """name → number of declared arguments, from the header text."""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for name, args in re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
+        out[name] = 0 if args.strip() == "void" else len(args.split(","))
+    return out
+
+
+def test_data_exports_match_the_header():
+    decl = declarations()
+    assert sorted(decl) == ["spnerf_data_abi_version", "spnerf_depth_priors", "spnerf_rpc_rays_f64",
+                            "spnerf_scene_bounds", "spnerf_semantic_labels"]
+    L = _data_lib.lib()
+    assert L is _lib.lib()
+    for name in ("spnerf_depth_priors", "spnerf_scene_bounds", "spnerf_semantic_labels"):
+        assert hasattr(L, name), name
+    assert sorted(_data_lib.SIGNATURES) == sorted(decl), "data signature table out of sync with the header"
+    for name, n_args in decl.items():
+        assert hasattr(L, name), name
+        assert len(_data_lib.SIGNATURES[name][1]) == n_args, name
+    assert (decl["spnerf_depth_priors"], decl["spnerf_scene_bounds"], decl["spnerf_semantic_labels"]) == (20, 8, 12)
+    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib):
+        assert not set(_data_lib.SIGNATURES) & set(other.SIGNATURES)
+    hdr = open(HEADER).read()
+    consts = dict(re.findall(r"#define (SPNERF_DATA_[A-Z_]+) \(?(-?\d+)\)?", hdr))
+    assert L.spnerf_data_abi_version() == int(consts["SPNERF_DATA_ABI_VERSION"]) == _data_lib.SPNERF_DATA_ABI_VERSION
+    assert int(consts["SPNERF_DATA_WORKSPACE_BYTES"]) == _data_lib.DATA_WORKSPACE_BYTES
+    assert int(consts["SPNERF_DATA_VOID_LABEL"]) == _data_lib.VOID_LABEL == -100
+    assert L.spnerf_abi_version() == 2                      # the older ABIs are untouched
+
+
+def test_argument_errors_are_reported():
+    import ctypes
+    L = _data_lib.lib()
+    rpc = (ctypes.c_double * 90)()
+    cen = (ctypes.c_float * 3)()
+
+    def depth(K=4, h=4, w=4, rng=1.0, pix=ONE, ws=ONE):
+        return L.spnerf_depth_priors(rpc, 0.0, 1.0, h, w, cen, rng, pix, ONE, ONE, K, 1.0, 0.0, ONE, ONE, ONE, ONE, ONE,
+                                     ws, None)
+
+    assert depth(pix=None) == -1 and b"NULL input" in L.spnerf_last_error()
+    assert depth(ws=None) == -1 and b"NULL output" in L.spnerf_last_error()
+    assert depth(K=0) == -1 and b"K = 0" in L.spnerf_last_error()
+    assert depth(K=17) == -1 and b"cannot be distinct" in L.spnerf_last_error()
+    assert depth(h=0) == -1 and b"bad image size" in L.spnerf_last_error()
+    assert depth(rng=0.0) == -1 and b"bad range" in L.spnerf_last_error()
+    assert L.spnerf_scene_bounds(rpc, 1.0, 0.0, 1.0, 4, 4, None, None) == -1 and b"NULL" in L.spnerf_last_error()
+    assert L.spnerf_scene_bounds(rpc, 0.0, 0.0, 1.0, 4, 4, ONE, None) == -1 and b"downscale" in L.spnerf_last_error()
+    assert L.spnerf_scene_bounds(rpc, 1.0, 0.0, 1.0, -1, 4, ONE, None) == -1 and b"rectangle" in L.spnerf_last_error()
+
+    def sem(raster=ONE, hs=8, ws=8, h=4, w=4, sd=8, dense=0):
+        return L.spnerf_semantic_labels(raster, 0, hs, ws, ONE, h, w, sd, dense, ONE, ONE, None)
+
+    assert sem(raster=None) == -1 and b"NULL" in L.spnerf_last_error()
+    assert sem(h=0) == -1 and b"bad size" in L.spnerf_last_error()
+    assert sem(sd=0) == -1 and b"sem_downscale" in L.spnerf_last_error()
+    assert sem(hs=7, dense=1) == -1 and b"no 1/8 downsampling" in L.spnerf_last_error()
+    assert L.spnerf_rpc_rays_f64(rpc, 1.0, 0.0, 1.0, None, 4, None, 1.0, None, ONE, 8, None) == -1
+    assert b"NULL pixel list" in L.spnerf_last_error()
+
+
+def test_dataset_module_imports_without_touching_the_gpu():
+    code = ("import sys, torch\n"
+            "import spnerf_amd\n"
+            "from spnerf_amd import dataset\n"
+            "assert spnerf_amd.dataset is dataset\n"
+            "assert not torch.cuda.is_initialized()\n"
+            "assert 'spnerf_amd._data_lib' not in sys.modules\n"
+            "print('ok')\n")
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
+
+
+def image(pts2d, h=6, w=5):
+    k = len(pts2d)
+    return dict(rpc={}, height=h, width=w, min_alt=0.0, max_alt=1.0, pts2d=np.asarray(pts2d, np.int64).reshape(-1, 2),
+                pts3d=np.zeros((k, 3), np.float32), correl=np.linspace(0.3, 1.0, k).astype(np.float32))
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    """The host checks come first: the library must not be loaded by a call that is refused."""
+    def boom():
+        raise AssertionError("the library was loaded before the arguments were checked")
+    monkeypatch.setattr(_data_lib, "lib", boom)
+    monkeypatch.setattr(_lib, "lib", boom)
+
+
+def test_depth_data_refuses_bad_keypoints_on_the_host(no_library):
+    from spnerf_amd import dataset
+    kw = dict(center=np.zeros(3, np.float32), range=1.0)
+    good = [(0, 0), (3, 0), (1, 2), (4, 5)]
+    with pytest.raises(ValueError, match=r"strictly increasing.*keypoint 2 \(1, 1\) comes before keypoint 1 \(3, 2\)"):
+        dataset.load_depth_data([image([(0, 0), (3, 2), (1, 1), (4, 5)])], **kw)       # unsorted
+    with pytest.raises(ValueError, match=r"keypoint 3 \(1, 2\) repeats keypoint 2 \(1, 2\)"):
+        dataset.load_depth_data([image([(0, 0), (3, 0), (1, 2), (1, 2)])], **kw)       # duplicate
+    with pytest.raises(ValueError, match=r"image 1: .*keypoint 1 \(0, 0\)"):
+        dataset.load_depth_data([image(good), image([(2, 0), (0, 0)])], **kw)          # the second image is named
+    with pytest.raises(ValueError, match="K == 0"):
+        dataset.load_depth_data([image([])], **kw)
+    with pytest.raises(ValueError, match=r"depth priors need img_downscale == 1"):
+        dataset.load_depth_data([image(good)], img_downscale=2, **kw)
+    with pytest.raises(ValueError, match=r"keypoint 3 \(5, 5\) is outside the 6 x 5 image"):
+        dataset.load_depth_data([image([(0, 0), (3, 0), (1, 2), (5, 5)])], **kw)
+    with pytest.raises(ValueError, match="4 keypoints but pts3d"):
+        dataset.load_depth_data([dict(image(good), pts3d=np.zeros((3, 3), np.float32))], **kw)
+    with pytest.raises(ValueError, match="no images"):
+        dataset.load_depth_data([], **kw)
+
+
+def test_semantic_and_scaling_argument_errors(no_library):
+    from spnerf_amd import dataset
+    metas = [dict(height=4, width=4)]
+    raster = np.zeros((8, 8), np.uint8)
+    with pytest.raises(ValueError, match="sem_downscale"):
+        dataset.load_semantic_data(raster, metas, {2: 0}, sem_downscale=0)
+    with pytest.raises(ValueError, match=r"must be \(Hs, Ws\)"):
+        dataset.load_semantic_data(raster[0], metas, {2: 0})
+    with pytest.raises(ValueError, match="no 1/8 downsampling"):
+        dataset.load_semantic_data(raster[:7], metas, {2: 0}, dense_ss=True)
+    with pytest.raises(ValueError, match="outside"):
+        dataset.load_semantic_data(raster, metas, {300: 0})
+    with pytest.raises(ValueError, match="integer class codes"):
+        dataset.load_semantic_data(raster.astype(np.float32), metas, {2: 0})
+    with pytest.raises(ValueError, match="no images"):
+        dataset.init_scaling_params([])
+    lut = dataset.label_lut({2: 0, 17: 4})
+    assert lut.dtype == np.int32 and lut.shape == (256,) and lut[2] == 0 and lut[17] == 4
+    assert (np.delete(lut, [2, 17]) == -100).all()
+
+
+def test_cpu_devices_and_tensors_are_refused():
+    import torch
+    from spnerf_amd import dataset
+    good = image([(0, 0), (3, 0), (1, 2), (4, 5)])
+    kw = dict(center=np.zeros(3, np.float32), range=1.0)
+    with pytest.raises(_lib.SpnerfError, match="MI355X"):
+        dataset.load_depth_data([good], device="cpu", **kw)
+    with pytest.raises(_lib.SpnerfError, match="MI355X"):
+        dataset.load_depth_data([dict(good, correl=torch.zeros(4))], **kw)
+    with pytest.raises(_lib.SpnerfError, match="MI355X"):
+        dataset.load_semantic_data(torch.zeros(8, 8, dtype=torch.uint8), [dict(height=4, width=4)], {2: 0})
+    with pytest.raises(_lib.SpnerfError, match="MI355X"):
+        dataset.init_scaling_params([dict(good)], device="cpu")

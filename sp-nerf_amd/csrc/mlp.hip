@@ -1505,6 +1505,12 @@ static bool train_heads_shape(const Ctx& c, int mode) {
            c.k.Ffeat16 >= 0 && c.k.Fnar16 >= 0 && c.out && c.heads_done && !g_zsave;
 }
 static bool train_heads_on(const Ctx& c, int mode) { return g_heads_epi == 2 && train_heads_shape(c, mode); }
+// the shapes the fused heads dX launch (heads_dx_bf16.hip) runs: W = 512, H = 256, no β, every head
+// or the solar pass, and the packed layout carries its weight streams
+static bool heads_dx_shape(const Ctx& c, int mode) {
+    const Dims& d = c.d;
+    return d.bf && !g_zsave && (mode == 0 || mode == 2) && d.W == 512 && d.H == 256 && !d.beta && c.k.BG16 >= 0;
+}
 static HeadsFusedArgs heads_args(const Ctx& c, int mode, int64_t hl, double* flop, double* bytes);
 // the training heads' arguments: what they store, and their counted work (the wide layers as
 // computed — the solar pass's Q runs all 2H columns — and the narrow heads; stored: feat (+ the
@@ -1588,8 +1594,8 @@ static int32_t forward_gemms(const Ctx& c, bool save, int mode, hipStream_t s, b
                 a.bsig = c.pk(c.k.bsig);
                 *sig_done = true;
             }
-            // tile-ordered D (fused_bwd >= 2) of the layers the dX chain reads (D_{L-1} feeds the ×D
-            // head GEMM: row-major), when the saving 128-point instance runs and no 64-point block
+            // tile-ordered D (fused_bwd >= 2) of the layers the dX chain reads (and D_{L-1} where the
+            // fused heads dX launch reads it), when the saving 128-point instance runs and no 64-point block
             // straddles two windows: the window starts on a block boundary and ends on one (or ends
             // the workspace).  A pass's later windows follow its first one's record.
             if (save) {
@@ -1597,8 +1603,12 @@ static int32_t forward_gemms(const Ctx& c, bool save, int mode, hipStream_t s, b
                 const bool aligned = pb % kDtileRows == 0 && (pe % kDtileRows == 0 || pe == pt);
                 int mask = 0;
                 if (pb == 0) {
-                    if (g_fused_bwd >= 2 && aligned && trunk_dtile_ok(a))
+                    if (g_fused_bwd >= 2 && aligned && trunk_dtile_ok(a)) {
                         for (int l = first; l < d.L - 1; ++l) mask |= 1 << l;
+                        // D_{L-1} too when, and only when, the fused heads dX launch will consume it
+                        // (option fused_heads_bwd; the four head GEMMs read it row-major)
+                        if (g_fused_heads_bwd && heads_dx_shape(c, mode)) mask |= 1 << (d.L - 1);
+                    }
                     dtile_set(c.ws, mask);
                 } else {
                     mask = dtile_get(c.ws);
@@ -1956,8 +1966,10 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
         SPN_TRY(sb.run(s2));
     }
     // 3 - 5 (their dX GEMMs): the training heads' fused dX chain (heads_dx_bf16.hip, option
-    // heads_dx) — dS2, dZQ's sun half, dZG's feat half and dZ_{L-1} in ONE launch, bit for bit the
-    // four GEMMs below; their weight gradients then follow on s2 as before
+    // fused_heads_bwd) — dS2, dZQ's sun half, dZG's feat half and dZ_{L-1} in ONE launch, bit for bit
+    // the four GEMMs below; their weight gradients then follow on s2 as before.  It runs only where
+    // the forward recorded D_{L-1} tile-ordered (the launch reads nothing else); the ×D GEMM of step
+    // 5 refuses such a buffer (the option changed between the forward and its backward)
     const int NQ = mode == 0 ? d.NQ : H;
     const int NG = mode == 0 ? d.NG : W;
     bool hdx = false;
@@ -1969,7 +1981,8 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
         h.Bs3 = c.k.Bs3_16; h.Bs2 = c.k.Bs2_16; h.BQ = c.k.BQ16; h.BG = c.k.BG16;
         h.P = P; h.ldQ = d.NQ; h.ldG = d.NG; h.HP = d.HP; h.kQ = d.NQ; h.kG = d.NG;
         h.mode = mode; h.sem = d.sem ? 1 : 0;
-        hdx = g_heads_dx && !zs && !d.beta && W == 512 && H == 256 && (mode == 0 || mode == 2) && heads_dx_bf16_ok(h);
+        h.dl_tiled = (dtile_get(c.ws) >> (d.L - 1)) & 1;
+        hdx = g_fused_heads_bwd && h.dl_tiled && heads_dx_shape(c, mode) && heads_dx_bf16_ok(h);
         if (hdx) {
             const double flop = 2.0 * P * ((double)H * H * 2 + (double)NQ * W + (double)NG * W);
             const double in = 2.0 * P * (3.0 * H + (mode == 0 ? H : 0) + (mode == 0 && d.sem ? H : 0) + W) + 4.0 * P;
@@ -2052,6 +2065,9 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
         g.Dmul = buf(c.w.Db[d.L - 1]); g.ld_dmul = W;
         if constexpr (BF) g.dmul_z = zs ? 1 : 0;
         if (!hdx) {
+            if constexpr (BF)
+                SPN_ARG(((dtile_get(c.ws) >> (d.L - 1)) & 1) == 0, "backward: D_{L-1} is tile-ordered; the xD head GEMM reads row-major D");
+            g_heads_bwd_path |= 2;
             SPN_TRY(G::nt(g, s));
             SPN_TRY(stream_dep(sd, s, s2));
         }
@@ -2121,7 +2137,7 @@ static int32_t backward_points(const Ctx& c, int mode, const float* packed, cons
             a.dZ[i - 1] = c.hb(c.w.Db[i - 1]);
         }
         a.P = P; a.L = d.L;
-        a.dtile = dtile_get(c.ws);  // as the forward wrote each layer's D
+        a.dtile = dtile_get(c.ws) & ((1 << (d.L - 1)) - 1);  // as the forward wrote each layer's D (D_{L-1}: the heads')
         if (tsum && d.skip > 0 && d.skip < d.L) {
             a.Rsum[0] = c.at(c.w.Rp0); a.rs_layer[0] = 0;
             a.Rsum[1] = c.at(c.w.Rp4); a.rs_layer[1] = d.skip;
@@ -2529,8 +2545,8 @@ using namespace spn;
 
 static int* option_slot(const char* name) {
     const std::string n(name);
-    // The product library's switches (at most 15): the default kernels and their one documented
-    // alternate each (INTEGRATION.md §Kernel selection), and one read-back.
+    // The product library's switches: the default kernels and their one documented alternate each
+    // (INTEGRATION.md §Kernel selection), and two read-backs.
     if (n == "fused_trunk") return &g_fused_trunk;        // 0: layer-by-layer trunk GEMMs
     if (n == "trunk_tile") return &g_trunk_tile;          // 64 / 128-point training tiles
     if (n == "trunk_heads") return &g_trunk_heads;        // 0: inference heads in their own launch
@@ -2542,6 +2558,8 @@ static int* option_slot(const char* name) {
     if (n == "defer_heads") return &g_defer_heads;        // the heads' weight gradients in the group launch
     if (n == "fused_bwd") return &g_fused_bwd;            // 0: the dX chain layer by layer; 1: row-major D; 2: tile-ordered D; 3: and 128-point chain tiles
     if (n == "trunk_bwd_tile") return &g_trunk_bwd_tile;  // read-back: tile sizes (64 | 128) of the dX chain launches since zeroed
+    if (n == "fused_heads_bwd") return &g_fused_heads_bwd;  // 0: the training heads' dX as four GEMMs
+    if (n == "heads_bwd_path") return &g_heads_bwd_path;  // read-back: 1 = the fused heads dX ran, 2 = the four GEMMs, since zeroed
     if (n == "tn_bf16_variant") return &g_tn16_variant;   // 1: 128x128 TN tiles, 2: register-staged 256x256
     if (n == "tn_bf16_k64") return &g_tn16_k64;           // 0: N = 512, K = 64 weight gradients on 128x128 tiles
     if (n == "nt_f32_variant") return &g_nt_variant;      // the fp32 (parity) NT GEMM tilings
@@ -2586,7 +2604,6 @@ static int* option_slot(const char* name) {
     if (n == "trunk2") return &g_trunk2;
     if (n == "trunk2_tile") return &g_trunk2_tile;
     if (n == "emu_bf16") return &g_emu_bf16;
-    if (n == "heads_dx") return &g_heads_dx;
 #endif
     return nullptr;
 }

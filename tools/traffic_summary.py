@@ -23,7 +23,7 @@ CLASSES = [(r"k_gemm_nt_bf16d<true", "gemm_nt_bf16d_dmul"), (r"k_gemm_nt_bf16d<"
            (r"k_heads_fwd", "heads_fwd"), (r"k_heads_bwd", "heads_bwd"), (r"k_tn_skinny", "tn_skinny"),
            (r"k_reduce_slabs", "reduce_slabs"), (r"k_encode", "encode"), (r"k_composite_fwd", "composite_fwd"),
            (r"k_composite_bwd", "composite_bwd"), (r"k_ray_rowsum", "ray_rowsum"),
-           (r"k_merge_rows", "merge_samples"), (r"k_heads_dx_bf16", "heads_dx")]
+           (r"k_merge_rows", "merge_samples"), (r"k_heads_dx128_bf16", "heads_dx")]
 
 
 def class_of(name):

@@ -37,6 +37,8 @@ constexpr int PART_OFF = OST_OFF + OST_BYTES;
 constexpr int RQ_OFF = PART_OFF + PART_BYTES;
 constexpr int LDS = RQ_OFF + RQ_BYTES;
 
+// NG: groups of four semantic classes (hd::heads_tile): 1 for C <= 4, 2 for C <= 8
+template <int NG>
 __global__ __launch_bounds__(512) void k_heads_bf16(HeadsFusedArgs g, PackedOffs k, int ntiles) {
     __shared__ __attribute__((aligned(16))) char smem[LDS];
     const int tid = threadIdx.x;
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(512) void k_heads_bf16(HeadsFusedArgs g, PackedOffs
             }
         }
         __syncthreads();
-        heads_tile<true>(g, k, smem, ost, part, srq, p0);
+        heads_tile<true, NG>(g, k, smem, ost, part, srq, p0);
         __syncthreads();  // the next tile restages the image
     }
 }
@@ -74,7 +76,8 @@ __global__ __launch_bounds__(512) void k_heads_bf16(HeadsFusedArgs g, PackedOffs
 // the trunk's tile loop spilled (64-bit values reloaded from scratch behind the copy-out stores)
 // and the main pass took 5.78 ms against 2.78 + 1.72 ms for the two launches.
 static_assert(SB_N * 4 <= RQ_BYTES, "the training heads' biases in the RQ area");
-template <bool RQ1, bool SOL>
+// NG: groups of four semantic classes (hd::heads_tile_train); the solar pass has no semantic head
+template <bool RQ1, bool SOL, int NG = 1>
 __global__ __launch_bounds__(512) void k_heads_train_bf16(HeadsFusedArgs g, PackedOffs k, int ntiles) {
     __shared__ __attribute__((aligned(16))) char smem[LDS];
     const int tid = threadIdx.x;
@@ -111,17 +114,17 @@ __global__ __launch_bounds__(512) void k_heads_train_bf16(HeadsFusedArgs g, Pack
         }
         const int r = opaque(tid);
         if (r < TM) ost[r * OST_LD + 3] = softplusf_(g.hsave[std::min<int64_t>(p0 + r, g.P - 1) * 8]);
-        if constexpr (RQ1) stage_rows_ost(g, k, ost, p0, tid);
+        if constexpr (RQ1) stage_rows_ost<NG == 1>(g, k, ost, p0, tid);
         __syncthreads();
         const int next = tile + (int)gridDim.x;
         // (past the last tile: this tile's rows again, never stored — no branch around the loads)
-        heads_tile_train<RQ1, SOL>(g, k, smem, ost, part, sbias, p0, [&] { load_hl((int64_t)std::min(next, ntiles - 1) * TM); });
+        heads_tile_train<RQ1, SOL, NG>(g, k, smem, ost, part, sbias, p0, [&] { load_hl((int64_t)std::min(next, ntiles - 1) * TM); });
         __syncthreads();  // the next tile restages the image
     }
 }
 
 bool heads_train_bf16_ok(const HeadsFusedArgs& h, const PackedOffs& k) {
-    return h.HL && (h.mode == 0 || h.mode == 2) && h.NO <= OST_LD && h.C <= 3 && h.G && h.Q && h.DQ && h.S2 && h.DS2 &&
+    return h.HL && (h.mode == 0 || h.mode == 2) && h.NO <= OST_LD && h.C <= kHeadsMaxC && h.G && h.Q && h.DQ && h.S2 && h.DS2 &&
            h.S3 && h.DS3 && h.hsave && (h.mode != 0 || h.C == 0 || h.DG) && h.ldG % 8 == 0 && h.ldQ % 8 == 0 &&
            k.Fnar16 >= 0 && k.Ffeat16 >= 0 && k.FQ16 >= 0 && k.FQs16 >= 0 && k.Fs2_16 >= 0 && k.Fs3_16 >= 0 &&
            (h.C == 0 || k.Fsem16 >= 0);
@@ -147,6 +150,9 @@ int32_t heads_train_bf16(const HeadsFusedArgs& a, const PackedOffs& k, hipStream
     if (a.mode == 2) {
         if (rq1) hipLaunchKernelGGL((k_heads_train_bf16<true, true>), grid, block, 0, s, ad, k, ntiles);
         else hipLaunchKernelGGL((k_heads_train_bf16<false, true>), grid, block, 0, s, ad, k, ntiles);
+    } else if (a.C > 4) {  // two class groups
+        if (rq1) hipLaunchKernelGGL((k_heads_train_bf16<true, false, 2>), grid, block, 0, s, ad, k, ntiles);
+        else hipLaunchKernelGGL((k_heads_train_bf16<false, false, 2>), grid, block, 0, s, ad, k, ntiles);
     } else {
         if (rq1) hipLaunchKernelGGL((k_heads_train_bf16<true, false>), grid, block, 0, s, ad, k, ntiles);
         else hipLaunchKernelGGL((k_heads_train_bf16<false, false>), grid, block, 0, s, ad, k, ntiles);
@@ -156,12 +162,12 @@ int32_t heads_train_bf16(const HeadsFusedArgs& a, const PackedOffs& k, hipStream
 }
 
 bool heads_bf16_shape_ok(const Dims& d) {
-    return d.bf && d.W == HW && d.H == HH && !d.beta && d.C <= 4 && d.NQ == 2 * d.H && d.NO <= OST_LD && d.sem_col == 8;
+    return d.bf && d.W == HW && d.H == HH && !d.beta && d.C <= kHeadsMaxC && d.NQ == 2 * d.H && d.NO <= OST_LD && d.sem_col == 8;
 }
 bool heads_bf16_supported(const Dims& d) { return g_fused_heads && heads_bf16_shape_ok(d); }
 
 int32_t heads_bf16(const HeadsFusedArgs& a, const PackedOffs& k, hipStream_t s, double flop, double bytes) {
-    SPN_ARG(a.P >= 0 && a.S > 0 && a.NO <= OST_LD && a.C <= 4, "heads_bf16: bad sizes");
+    SPN_ARG(a.P >= 0 && a.S > 0 && a.NO <= OST_LD && a.C <= kHeadsMaxC, "heads_bf16: bad sizes (C <= %d)", kHeadsMaxC);
     SPN_ARG(k.Fnar16 >= 0, "heads_bf16: narrow heads not packed");
     SPN_ARG(a.mode == 1 || (k.Ffeat16 >= 0 && k.FQ16 >= 0 && k.Fs2_16 >= 0 && k.Fs3_16 >= 0 && (a.C == 0 || k.Fsem16 >= 0)),
             "heads_bf16: weights not packed for the fused heads");
@@ -172,7 +178,9 @@ int32_t heads_bf16(const HeadsFusedArgs& a, const PackedOffs& k, hipStream_t s, 
     ad.nt = (g_trunk_nt >> 1) & 1;
     ad.dbg = g_heads_dbg;
     ProfScope prof("heads_fused", s, flop, bytes);
-    hipLaunchKernelGGL(k_heads_bf16, dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, k, ntiles);
+    const dim3 grid(std::min(ntiles, num_cus())), block(512);
+    if (a.C > 4) hipLaunchKernelGGL(k_heads_bf16<2>, grid, block, 0, s, ad, k, ntiles);
+    else hipLaunchKernelGGL(k_heads_bf16<1>, grid, block, 0, s, ad, k, ntiles);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }

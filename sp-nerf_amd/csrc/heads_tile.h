@@ -129,7 +129,11 @@ constexpr int RQ_BYTES = RQ_RAYS * 2 * HH * 4;     // per-ray Q rows of up to RQ
 // 8-wave workgroup calls it (it contains barriers); on return the image may be overwritten.
 // GA / KA: HeadsFusedArgs / PackedOffs, possibly address-space qualified (the fused trunk passes
 // references into the kernarg segment)
-template <bool RQ, typename GA, typename KA>
+// NG: groups of four semantic classes (C <= 4·NG).  part holds one group's partials: with two
+// groups the first is folded into ost (its final place: nothing else touches the logits' columns
+// before the outputs are written), then the second group's pass over the semantic accumulators
+// takes its slots.  Per class the sum stays the 8 waves' partials in wave order, whatever the group.
+template <bool RQ, int NG = 1, typename GA, typename KA>
 __device__ __forceinline__ void heads_tile(GA& g, KA& k, char* smem, float* ost, float* part, float* srq, int64_t p0) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const float* Pk = g.packed;
@@ -191,36 +195,55 @@ __device__ __forceinline__ void heads_tile(GA& g, KA& k, char* smem, float* ost,
             layer_mm<1>(stream(k.Fsem16, HW / 16, 1), HW / 16, smem, lane, acc, ring1);
             // logits partials over this wave's 32 features, per point (lane halves hold 4 + 4)
             const int el = opaque(lane), er32 = el & 31, eh = el >> 5;
-            float sacc[NJ][4];
+            // one pass per class group over the accumulators (still live: the second pass
+            // recomputes the sines instead of holding eight classes' weights and sums at once)
+            auto sem_group = [&](auto kc0) {
+                constexpr int c0 = decltype(kc0)::value;
+                float sacc[NJ][4];
 #pragma unroll
-            for (int j = 0; j < NJ; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                for (int c = 0; c < 4; ++c) sacc[j][c] = 0.f;
+                    for (int c = 0; c < 4; ++c) sacc[j][c] = 0.f;
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                const int f0 = 32 * w + 8 * gq + 4 * eh;
-                const f32x4 bv = ld4(Pk + k.bG + HW + f0);
-                f32x4 wm[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) wm[c] = c < C ? ld4(Pk + k.Wm2 + c * HH + f0) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) {
-                    float y[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = (float)(bf16)fast_sin(acc[0][j][4 * gq + e] + bv[e]);
+                for (int gq = 0; gq < 4; ++gq) {
+                    const int f0 = 32 * w + 8 * gq + 4 * eh;
+                    const f32x4 bv = ld4(Pk + k.bG + HW + f0);
+                    f32x4 wm[4];
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
-                        sacc[j][c] += (y[0] * wm[c][0] + y[1] * wm[c][1]) + (y[2] * wm[c][2] + y[3] * wm[c][3]);
+                        wm[c] = c0 + c < C ? ld4(Pk + k.Wm2 + (c0 + c) * HH + f0) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) {
+                        float y[4];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) y[e] = (float)(bf16)fast_sin(acc[0][j][4 * gq + e] + bv[e]);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            sacc[j][c] += (y[0] * wm[c][0] + y[1] * wm[c][1]) + (y[2] * wm[c][2] + y[3] * wm[c][3]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const float s = sacc[j][c] + __shfl_xor(sacc[j][c], 32, 64);
+                        if (eh == 0 && c0 + c < C) part[(w * TM + 32 * j + er32) * 4 + c] = s;
+                    }
+            };
+            sem_group(std::integral_constant<int, 0>{});
+            if constexpr (NG == 2) {
+                // classes 0..3 leave part for ost, then classes 4..7 take their slots
+                __syncthreads();
+                {
+                    const int i = opaque(tid), r = i >> 2, c = i & 3;  // 512 threads: 128 points x 4 classes
+                    float s = 0.f;
+                    for (int v = 0; v < 8; ++v) s += part[(v * TM + r) * 4 + c];
+                    if (c < C) ost[r * OST_LD + g.sem_col + c] = s + Pk[k.bm2 + c];
+                }
+                __syncthreads();
+                sem_group(std::integral_constant<int, 4>{});
             }
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float s = sacc[j][c] + __shfl_xor(sacc[j][c], 32, 64);
-                    if (eh == 0 && c < C) part[(w * TM + 32 * j + er32) * 4 + c] = s;
-                }
         }
         // feat (linear, 512) → the image
         __builtin_amdgcn_sched_barrier(0);
@@ -269,11 +292,20 @@ __device__ __forceinline__ void heads_tile(GA& g, KA& k, char* smem, float* ost,
         }
         // semantic logits: the 8 waves' partials in wave order
         __builtin_amdgcn_sched_barrier(0);
-        for (int i = tid; i < TM * C; i += 512) {
-            const int r = i / C, c = i % C;
-            float s = 0.f;
-            for (int v = 0; v < 8; ++v) s += part[(v * TM + r) * 4 + c];
-            ost[r * OST_LD + g.sem_col + c] = s + Pk[k.bm2 + c];
+        if constexpr (NG == 2) {  // (classes 0..3 are in ost already)
+            const int i = opaque(tid), r = i >> 2, c = 4 + (i & 3);
+            if (c < C) {
+                float s = 0.f;
+                for (int v = 0; v < 8; ++v) s += part[(v * TM + r) * 4 + (c - 4)];
+                ost[r * OST_LD + g.sem_col + c] = s + Pk[k.bm2 + c];
+            }
+        } else {
+            for (int i = tid; i < TM * C; i += 512) {
+                const int r = i / C, c = i % C;
+                float s = 0.f;
+                for (int v = 0; v < 8; ++v) s += part[(v * TM + r) * 4 + c];
+                ost[r * OST_LD + g.sem_col + c] = s + Pk[k.bm2 + c];
+            }
         }
         // albedo from rgb1 (image k-steps 16..31) on MFMA
         __syncthreads();  // the logits are read from part
@@ -536,15 +568,17 @@ constexpr int SB_G = 0, SB_Q = HW + HH, SB_S2 = SB_Q + 2 * HH, SB_S3 = SB_S2 + H
 // epilogues)
 // The training heads' per-tile staging in ost (the caller's, before the barrier that precedes
 // heads_tile_train<true>; every tile within one ray): the ray's Q rows rbQ[ray][0..512) in columns
-// 8..15 of rows 0..63 and (SPN_HEADS_WM_OST) the semantic logits' weights W_m2 [C][HH], C <= 3:
-// entries q < 512 in columns 4..7 (rows q / 4), the rest in columns 8..15 of rows 64 + (q - 512) / 8
+// 8..15 of rows 0..63 and (SPN_HEADS_WM_OST) the semantic logits' weights W_m2 [C][HH], C <= 4
+// (1 024 floats): entries q < 512 in columns 4..7 (rows q / 4), the rest in columns 8..15 of rows 64 + (q - 512) / 8
 // — every f32x4 the epilogues read is one aligned piece of a row.  Columns 0..2 and 4..15 are free
 // until the semantic logits and the outputs are written, after the Q epilogue.
-template <typename GA, typename KA>
+// WM false (the two-group instance, 4 < C <= 8): W_m2 is not staged — eight classes do not fit,
+// and columns 4..7 keep the first group's logits until the Q epilogue has consumed the Q rows.
+template <bool WM = true, typename GA, typename KA>
 __device__ __forceinline__ void stage_rows_ost(GA& g, KA& k, float* ost, int64_t p0, int tid_) {
     const int f = opaque(tid_);  // 512 threads: the 2·HH floats of the row
     ost[(f >> 3) * OST_LD + 8 + (f & 7)] = g.rbQ[(int64_t)((int)p0 / g.S) * (2 * HH) + f];
-    if constexpr (SPN_HEADS_WM_OST) {
+    if constexpr (SPN_HEADS_WM_OST && WM) {
         if (g.mode == 0)  // block-uniform (the solar pass has no semantic head)
             for (int q = f; q < g.C * HH; q += 512)
                 ost[q < 512 ? (q >> 2) * OST_LD + 4 + (q & 3) : (64 + ((q - 512) >> 3)) * OST_LD + 8 + ((q - 512) & 7)] =
@@ -553,7 +587,12 @@ __device__ __forceinline__ void stage_rows_ost(GA& g, KA& k, float* ost, int64_t
 }
 
 // SOL: the solar pass (g.mode 2), its own instance: sun1 alone in Q, no semantic / albedo heads
-template <bool RQ1, bool SOL, typename GA, typename KA, typename Prefetch>
+// NG: groups of four semantic classes (C <= 4·NG).  With two groups the logits' weights come from
+// L2 (not staged in ost), the first group's logits (the 8 waves' partials in wave order + bias,
+// as with one group) are folded into ost columns 4..7 and move to their columns once the Q
+// epilogue is done with columns 8..15, and the second group runs as a second pass over the
+// semantic accumulators, its partials in part's slots.
+template <bool RQ1, bool SOL, int NG = 1, typename GA, typename KA, typename Prefetch>
 __device__ __forceinline__ void heads_tile_train(GA& g, KA& k, char* smem, float* ost, float* part, const float* sbias,
                                                  int64_t p0, Prefetch&& prefetch) {
     constexpr int D1 = 8;  // ring depth of the 256-wide layers (sem hidden, sun_v 2 / 3)
@@ -601,7 +640,8 @@ __device__ __forceinline__ void heads_tile_train(GA& g, KA& k, char* smem, float
         u32x4 ring1[D1][1];
         layer_prime_n<1, D1>(stream(k.Fsem16, HW / 16, 1), ring1);
         layer_mm_d<1, D1>(stream(k.Fsem16, HW / 16, 1), HW / 16, smem, lane, acc, ring1, nodrain);
-        layer_prime_n<2, D2>(stream(k.Ffeat16, HW / 16, 2), ring2f);
+        // (two groups: feat's ring is primed between the passes, its registers free in the first)
+        if constexpr (NG == 1) layer_prime_n<2, D2>(stream(k.Ffeat16, HW / 16, 2), ring2f);
         const auto rsG = rsrc_r(g.G, g.ldG), rsD = rsrc_r(g.DG, g.ldG);
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
@@ -621,9 +661,10 @@ __device__ __forceinline__ void heads_tile_train(GA& g, KA& k, char* smem, float
                 for (int c = 0; c < 4; ++c) {
                     f32x4 wm = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (c < C) {
-                        if constexpr (RQ1 && SPN_HEADS_WM_OST)  // staged in ost (see the top of the tile)
+                        if constexpr (RQ1 && SPN_HEADS_WM_OST && NG == 1)  // staged in ost (see the top of the tile)
                             wm = *reinterpret_cast<const f32x4*>(
-                                ost + (c < 2 ? (c * 64 + 8 * w + 2 * gq + eh) * OST_LD + 4 : (64 + 4 * w + gq) * OST_LD + 8 + 4 * eh));
+                                ost + (c < 2 ? (c * 64 + 8 * w + 2 * gq + eh) * OST_LD + 4
+                                             : (64 + 32 * (c - 2) + 4 * w + gq) * OST_LD + 8 + 4 * eh));
                         else
                             wm = ld4(Pk + k.Wm2 + c * HH + f0);
                     }
@@ -638,6 +679,44 @@ __device__ __forceinline__ void heads_tile_train(GA& g, KA& k, char* smem, float
                 if (eh == 0 && c < C) part[(w * TM + 32 * j + er32) * 4 + c] = t;
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (NG == 2) {
+            // classes 0..3: the 8 waves' partials in wave order + bias into ost columns 4..7
+            __syncthreads();
+            {
+                const int i = opaque(tid), r = i >> 2, c = i & 3;  // 512 threads: 128 points x 4 classes
+                float t = 0.f;
+                for (int v = 0; v < 8; ++v) t += part[(v * TM + r) * 4 + c];
+                ost[r * OST_LD + 4 + c] = t + Pk[k.bm2 + c];
+            }
+            __syncthreads();
+            layer_prime_n<2, D2>(stream(k.Ffeat16, HW / 16, 2), ring2f);
+            // classes 4..7 over the accumulators again (still live; the same sincos and rounding
+            // as the stored hidden values) instead of eight classes' weights and sums at once
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                float sacc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int gq = 0; gq < 4; ++gq) {
+                    const int f0 = 32 * w + 8 * gq + 4 * eh;
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(sbias + SB_G + HW + f0);
+                    float y[4], cs[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sincos(acc[0][j][4 * gq + e] + bv[e], &y[e], &cs[e]);
+                    const f32x4 yb = raw_f32(u32x2{pack2(y[0], y[1]), pack2(y[2], y[3])});
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const f32x4 wm = 4 + c < C ? ld4(Pk + k.Wm2 + (4 + c) * HH + f0) : f32x4{0.f, 0.f, 0.f, 0.f};
+                        sacc[c] += (yb[0] * wm[0] + yb[1] * wm[1]) + (yb[2] * wm[2] + yb[3] * wm[3]);
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float t = sacc[c] + __shfl_xor(sacc[c], 32, 64);
+                    if (eh == 0 && 4 + c < C) part[(w * TM + 32 * j + er32) * 4 + c] = t;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     } else {
         layer_prime_n<2, D2>(stream(k.Ffeat16, HW / 16, 2), ring2f);
@@ -799,6 +878,17 @@ __device__ __forceinline__ void heads_tile_train(GA& g, KA& k, char* smem, float
         for (int i = opaque(tid); i < TM * C; i += 512) {
             const int r = i / C, c = i % C;
             float t = 0.f;
+            if constexpr (NG == 2) {
+                // classes 0..3 were folded (bias included) into columns 4..7; part holds 4..7's
+                if (c < 4) {
+                    t = ost[r * OST_LD + 4 + c];
+                } else {
+                    for (int v = 0; v < 8; ++v) t += part[(v * TM + r) * 4 + (c - 4)];
+                    t += Pk[k.bm2 + c];
+                }
+                ost[r * OST_LD + g.sem_col + c] = t;
+                continue;
+            }
             for (int v = 0; v < 8; ++v) t += part[(v * TM + r) * 4 + c];
             ost[r * OST_LD + g.sem_col + c] = t + Pk[k.bm2 + c];
         }

@@ -1498,10 +1498,11 @@ static bool trunk_l0_on(const Ctx& c, bool save) {
 }
 
 // option heads_epi 2: the training forward's heads (k_heads_train_bf16) as one launch after the
-// saving trunk, where the shape allows: W = 512, H = 256, no β head, C <= 3
+// saving trunk, where the shape allows: W = 512, H = 256, no β head, C <= kHeadsMaxC (8: one kernel
+// instance per group count of four classes); a larger C falls back to the layer-by-layer heads
 static bool train_heads_shape(const Ctx& c, int mode) {
     const Dims& d = c.d;
-    return d.bf && (mode == 0 || mode == 2) && d.W == 512 && d.H == 256 && !d.beta && (!d.sem || d.C <= 3) &&
+    return d.bf && (mode == 0 || mode == 2) && d.W == 512 && d.H == 256 && !d.beta && (!d.sem || d.C <= kHeadsMaxC) &&
            c.k.Ffeat16 >= 0 && c.k.Fnar16 >= 0 && c.out && c.heads_done && !g_zsave;
 }
 static bool train_heads_on(const Ctx& c, int mode) { return g_heads_epi == 2 && train_heads_shape(c, mode); }
@@ -1624,7 +1625,9 @@ static int32_t forward_gemms(const Ctx& c, bool save, int mode, hipStream_t s, b
             const double bytes = in + 2.0 * P * W * nout + (a.X0b_out ? 2.0 * P * d.K0p : 0.0);
             if constexpr (BF) {
                 // inference: the fused heads on the trunk's last LDS image (no H_L in HBM)
-                if (c.heads_done && c.out && heads_fused_on(c, save, mode) && (trunk1_heads_ok(a) || trunk2_heads_ok(a))) {
+                if (c.heads_done && c.out && heads_fused_on(c, save, mode) &&
+                    // (the two-workgroup ablation kernel's heads: one class group only)
+                    (trunk1_heads_ok(a) || (trunk2_heads_ok(a) && (!d.sem || d.C <= 4)))) {
                     double hflop = 0.0, hbytes = 0.0;
                     const HeadsFusedArgs h = heads_args(c, mode, -1, &hflop, &hbytes);
                     // algorithmic bytes: the trunk's input, the output rows (H_L never leaves)
@@ -1708,7 +1711,8 @@ static int32_t forward_gemms(const Ctx& c, bool save, int mode, hipStream_t s, b
     T* S2buf = save ? G::buf(c, c.w.S2) : G::buf(c, c.w.Hb[((d.L - 1) & 1) ^ 1]);
     T* S3buf = save ? G::buf(c, c.w.S3) : G::buf(c, c.w.Hb[2]);
     // option heads_epi: the narrow heads in the G / Q / sun_v.3 epilogues (bf16 DMA NT with the
-    // bias / per-ray-row epilogue; σ from the trunk's hsave column)
+    // bias / per-ray-row epilogue; σ from the trunk's hsave column); its epilogue holds three
+    // outputs per head in registers, so C <= 3 here (more classes: the wave-per-point heads below)
     const bool hepi = BF && g_heads_epi && g_nt16_epi && (g_nt16_ip_gen == 2 || g_nt16_ip_gen == 3) && !zs && g_nt16_variant == 8 && save &&
                       sig_done && *sig_done && c.out && c.heads_epi_done &&
                       W == 512 && H == 256 && (!d.sem || d.C <= 3) && S % 32 == 0 && mode != 1 &&
@@ -1856,7 +1860,7 @@ static int32_t mlp_forward(const Dims& d, const float* packed, const float* rays
         ProfScope prof("heads_fwd", s, 2.0 * P * ((sig_done ? 0 : W) + (mode != 1 ? 4 * H + H * d.C : 0)),
                        (d.bf ? 2.0 : 4.0) * P * ((sig_done ? 0 : W) + 3 * H) + 4.0 * P * (d.NO + (sig_done ? 1 : 0)));
         const int nc = g_heads_variant == 0 ? 0 : cdiv(W, 256);
-        const size_t lds = mode == 0 && d.sem ? sizeof(float) * d.C * (H + 1) : 0;  // ≤ 32 × 513 floats when nc ≤ 4
+        const size_t lds = mode == 0 && d.sem ? sizeof(float) * d.C * (H + 1) : 0;  // C × 257 floats (8 224 B at C = 8; the kernel runs for any C the LDS limit allows)
         auto launch = [&](auto a) {
             using T = std::remove_cv_t<std::remove_pointer_t<decltype(a.HL)>>;
             if (sig_done && nc == 2) {  // σ from hsave (W = 512, bf16)

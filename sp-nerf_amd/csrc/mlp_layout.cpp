@@ -278,8 +278,13 @@ WS ws_layout(const Dims& d, int64_t n_rays, int32_t S, int32_t flags) {
         // ≤ 9 rows x max(W, H) columns each, mlp.hip SkinnyBatch)
         // chunks of any row count up to P (resp. B): skinny_chunk's bound
         const int64_t cP = std::min<int64_t>((P + 63) / 64, 768), cB = std::min<int64_t>((B + 63) / 64, 768);
-        w.sk_slab_n = std::max(cP * 9 * W, cB * kSkinnyMulti * 9 * W);
-        w.sk_slab_b_n = std::max(cP * 9, cB * kSkinnyMulti * 9);
+        // the point batch of a backward (mlp.hip step 2): σ (1 x W), sun (1 x H), albedo (3 x H), β
+        // (1 x H) and the C semantic logits (C x H) — 5 + C rows, more than 9 from five classes on
+        // (at point counts small enough for one chunk per 64 points, the backward of a 5-class model
+        // stopped at "skinny batch: slab capacity")
+        const int64_t prow = std::max<int64_t>(9, 5 + d.C), pcol = std::max<int64_t>(9 * W, W + (int64_t)(4 + d.C) * H);
+        w.sk_slab_n = std::max(cP * pcol, cB * kSkinnyMulti * 9 * W);
+        w.sk_slab_b_n = std::max(cP * prow, cB * kSkinnyMulti * 9);
         w.sk_slab = take(w.sk_slab_n);
         w.sk_slab_b = take(w.sk_slab_b_n);
     }

@@ -218,8 +218,10 @@ __host__ __device__ inline int64_t frag_off(int n, int k, int Kp, int NA) {
 // σ = softplus(w_σ·H + b); semantic hidden = sin(W_m1 H + b) → logits (its C dot products in
 // the epilogue); feat = W_f H + b; [sun1 | rgb1] = sin(W_Q feat + b + per-ray sun rows);
 // albedo from rgb1; sun2 = sin(W_s2 sun1 + b); sun3 = sin(W_s3 sun2 + b); sun = sigmoid(w_s4
-// sun3 + b); sky from the per-ray rows.  W = 512, H = 256, no β head, C ≤ 4
-// (models/spnerf.py:332-367).
+// sun3 + b); sky from the per-ray rows.  W = 512, H = 256, no β head, C ≤ kHeadsMaxC: the logits'
+// narrow part works in groups of four classes, one group (C ≤ 4) or two (C ≤ 8) per kernel
+// instance, and the output staging row holds NO = 8 + C ≤ 16 floats (models/spnerf.py:332-367).
+constexpr int kHeadsMaxC = 8;
 struct HeadsFusedArgs {
     const bf16* HL = nullptr;
     const float* packed = nullptr;

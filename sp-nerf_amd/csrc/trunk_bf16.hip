@@ -106,6 +106,8 @@ __device__ __forceinline__ int x0_rel(int row, int ch) { return row * 128 + ((ch
 // the trunk's LDS, their partials overlay the PE tile (restaged by the next tile), and the weight
 // ring is primed per tile instead of running on through the heads.  The heads' arguments are read
 // per tile through an opaque kernarg pointer (not hoisted into registers live through the layers).
+// VAR 4096 | 16384: the heads with two groups of four semantic classes (4 < C <= 8), their own
+// instance so that the one-group kernel keeps its registers.
 template <int TMt, int VAR = 0>
 __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 4096) != 0, TrunkHeadsArgs, TrunkArgs> g,
                                                     int ntiles) {
@@ -113,6 +115,8 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
     constexpr int NJ = Geo::NJ, IMG = Geo::IMG, CPT = Geo::CPT;
     constexpr int TPD = Geo::TPD;
     constexpr bool HEADS = (VAR & 4096) != 0;
+    constexpr int HNG = (VAR & 16384) ? 2 : 1;  // the heads' class groups
+    static_assert(!(VAR & 16384) || HEADS, "class groups: the fused heads' instances");
     static_assert(!HEADS || (TMt == 128 && Geo::BIAS_OFF - Geo::X0_OFF >= hd::PART_BYTES &&
                              Geo::LDS + hd::OST_BYTES <= 160 * 1024), "the fused heads: 128-point tiles, LDS");
     constexpr bool NOMF = VAR & 16, NOSIN = VAR & 32, NOW = VAR & 64, NOB = VAR & 128, NOEPI = VAR & 256;
@@ -834,7 +838,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 40
                         typedef const __attribute__((address_space(4))) TrunkHeadsArgs* KH;
                         KH kh = (KH)__builtin_amdgcn_kernarg_segment_ptr();
                         asm volatile("" : "+s"(kh));  // opaque per tile: the heads' argument loads stay here
-                        hd::heads_tile<false>(kh->hg, kh->hk, smem, reinterpret_cast<float*>(smem + Geo::LDS),
+                        hd::heads_tile<false, HNG>(kh->hg, kh->hk, smem, reinterpret_cast<float*>(smem + Geo::LDS),
                                               reinterpret_cast<float*>(smem + Geo::X0_OFF), nullptr, p0);
                     } else {
                         copy_all(smem, Hs, p0);
@@ -1356,7 +1360,7 @@ bool trunk1_heads_ok(const TrunkArgs& a) {
 int32_t trunk1_heads_bf16(const TrunkArgs& a, const HeadsFusedArgs& h, const PackedOffs& k, hipStream_t s, double flop,
                           double bytes) {
     SPN_ARG(trunk1_heads_ok(a), "trunk1_heads_bf16: unsupported shape or option");
-    SPN_ARG(h.P == a.P && h.S == a.S && h.NO <= hd::OST_LD && h.C <= 4 && k.Fnar16 >= 0, "trunk1_heads_bf16: bad heads");
+    SPN_ARG(h.P == a.P && h.S == a.S && h.NO <= hd::OST_LD && h.C <= kHeadsMaxC && k.Fnar16 >= 0, "trunk1_heads_bf16: bad heads (C <= %d)", kHeadsMaxC);
     SPN_ARG(!a.rays || (a.z && a.rs > 0 && !a.X0), "trunk1_heads_bf16: inline encoding needs z and rs");
     if (a.P == 0) return SPNERF_OK;
     SPN_ARG(a.P < (1ll << 31) / TW, "trunk1_heads_bf16: too many points (%lld)", (long long)a.P);
@@ -1371,7 +1375,9 @@ int32_t trunk1_heads_bf16(const TrunkArgs& a, const HeadsFusedArgs& h, const Pac
     ad.hg.dbg = 0;
     ad.hk = k;
     ProfScope prof("trunk_heads_bf16", s, flop, bytes);
-    hipLaunchKernelGGL((k_trunk_bf16<128, 4096>), dim3(std::min(ntiles, num_cus())), dim3(512), 0, s, ad, ntiles);
+    const dim3 grid(std::min(ntiles, num_cus())), block(512);
+    if (h.C > 4) hipLaunchKernelGGL((k_trunk_bf16<128, 4096 | 16384>), grid, block, 0, s, ad, ntiles);
+    else hipLaunchKernelGGL((k_trunk_bf16<128, 4096>), grid, block, 0, s, ad, ntiles);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }

@@ -22,6 +22,8 @@ from . import view  # noqa: F401  (whole views: image products and the validatio
 from .view import render_image, view_metrics  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
+from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)
+from .perceptual import LpipsWeights, lpips  # noqa: F401
 from . import losses  # noqa: F401  (modules/metrics.py, and the fused training losses)
 from .losses import FusedRenderLoss, FusedTrainLoss  # noqa: F401
 from . import dataset  # noqa: F401  (depth priors, semantic labels and scene.loc: satellite_scene.py on the GPU)

@@ -17,7 +17,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _image_lib, _lib, _view_lib, image
+from . import _image_lib, _lib, _lpips_lib, _view_lib, image, perceptual
 from .rendering import _coarse_rows, _fine_rows
 from .rng import current_random_source, device_key
 from .spnerf import composite, max_points_per_call
@@ -150,7 +150,7 @@ def render_image(models, args, rays, ts=None, semantics=None, *, chunk=None,
 
 
 def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_classes=0, hw=None, ssim_layout="hwc",
-                 window_size=3) -> dict:
+                 window_size=3, lpips=None) -> dict:
     """The scores the validation step logs, of a rendered view against its targets, in one pass on
     the device and one device-to-host copy: ``mse``, ``psnr`` (metrics.py:197-207, summed in fp64)
     and — with ``labels`` (int64, any label outside [0, num_classes) ignored, −100 included) and
@@ -165,7 +165,12 @@ def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_cla
     channel, on the same stream and in the same copy.  ``ssim_layout="hwc"`` reads the (H·W, 3)
     buffers as the interleaved image they are (eval.py:393); ``"chw"`` reads them as three H x W
     planes, which is what main.py:261's ``.view(1, 3, H, W)`` scores.  Without ``hw`` the result has
-    neither key."""
+    neither key.
+
+    With ``hw`` and ``lpips=`` an ``LpipsWeights`` the view is scored with LPIPS too (eval.py:128-135,
+    399: AlexNet features, the images taken as [0, 1] and read in ``ssim_layout``):
+    ``lpips`` and ``lpips_layers``, its five per-tap terms, again on the same stream and in the same
+    copy.  Without the argument neither key nor any of its launches is there."""
     if isinstance(planes_or_rgb, dict):
         rgb = planes_or_rgb["rgb"]
         if sem_class is None and labels is not None:
@@ -195,19 +200,26 @@ def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_cla
             raise ValueError(f"hw {tuple(hw)} is not the view's {n} rays")
         if ssim_layout not in ("hwc", "chw"):
             raise ValueError(f"ssim_layout {ssim_layout!r} is neither 'hwc' nor 'chw'")
+    elif lpips is not None:
+        raise ValueError("lpips= scores the view as an image: it needs hw=(H, W)")
     L = _view_lib.lib()
     nbytes = L.spnerf_view_metrics_workspace_bytes(n, C)
     if nbytes < 0:
         _lib.check(int(nbytes), "view_metrics_workspace_bytes")
     ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=rgb.device)
     vm_bytes = ctypes.sizeof(_view_lib.ViewMetricsResult)      # both result structs in one buffer: one copy
-    res = torch.zeros(vm_bytes + (image.RESULT_BYTES if hw is not None else 0), dtype=torch.uint8, device=rgb.device)
+    lp_off = vm_bytes + image.RESULT_BYTES
+    res = torch.zeros(vm_bytes + (image.RESULT_BYTES if hw is not None else 0) + (perceptual.RESULT_BYTES if lpips is not None else 0),
+                      dtype=torch.uint8, device=rgb.device)
     _lib.check(L.spnerf_view_metrics(n, _lib.ptr(rgb), _lib.ptr(tgt), _lib.ptr(sem_class if scored else None),
                                      _lib.ptr(labels if scored else None), C, _lib.ptr(ws), _lib.ptr(res),
                                      _lib.stream_of(rgb)), "view_metrics")
     if hw is not None:
         image.launch_ssim(rgb, tgt, 3, H, W, (1, 3 * W, 3) if ssim_layout == "hwc" else (H * W, W, 1), window_size, 1.0,
                           res.data_ptr() + vm_bytes)
+        if lpips is not None:
+            perceptual.launch_lpips(rgb, tgt, H, W, (1, 3 * W, 3) if ssim_layout == "hwc" else (H * W, W, 1), True, lpips,
+                                    res.data_ptr() + lp_off)
     raw = res.cpu().numpy().tobytes()                          # the one copy
     host = _view_lib.ViewMetricsResult.from_buffer_copy(raw)
     result = {"mse": host.mse, "psnr": host.psnr, "n": host.n, "miou": None, "oa": None, "correct": None, "confusion": None}
@@ -217,6 +229,9 @@ def view_metrics(planes_or_rgb, target_rgb, sem_class=None, labels=None, num_cla
     if hw is not None:
         sr = _image_lib.SsimResult.from_buffer_copy(raw, vm_bytes)
         result.update(ssim=sr.ssim, ssim_channels=[sr.channel_mean[c] for c in range(3)])
+        if lpips is not None:
+            lr = _lpips_lib.LpipsResult.from_buffer_copy(raw, lp_off)
+            result.update(lpips=lr.lpips, lpips_layers=list(lr.layer))
     return result
 
 

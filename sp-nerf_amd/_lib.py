@@ -161,7 +161,7 @@ def require_device(*tensors) -> None:
 
 class OptionUnavailable(SpnerfError):
     """A kernel switch the loaded library does not have: the A/B switches of kernels measured
-    slower than the defaults exist only in a -DSPN_ABLATIONS build."""
+    slower than the defaults exist only in a -DSPN_ABLATIONS build (csrc/ablations/)."""
 
 
 def has_option(name: str) -> bool:

@@ -29,19 +29,22 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "heads_tile.h"
-#include "trunk.h"
+#include "../heads_tile.h"
+#include "../trunk.h"
+
+#ifndef SPN_ABLATIONS
+#error "ablations/trunk2_bf16.hip belongs to -DSPN_ABLATIONS builds only (the product's stubs: trunk_bf16.hip)"
+#endif
 
 namespace spn {
 
 // Measured slower than the one-workgroup k_trunk_bf16 since round 4 (comments below): the kernel is
 // compiled only into -DSPN_ABLATIONS builds; the product build keeps the option variables, and its
-// trunk2_supported / trunk2_heads_ok are false.
+// trunk2_supported / trunk2_heads_ok are false (the end of trunk_bf16.hip).
 int g_trunk2 = 0;
 int g_trunk2_tile = 128;
 int g_trunk_heads = 2;
 
-#ifdef SPN_ABLATIONS
 #if SPN_TRUNK_KMAJOR
 #error "trunk2_bf16.hip reads the wave-contiguous fragment streams (SPN_TRUNK_KMAJOR 0)"
 #endif
@@ -552,31 +555,13 @@ int32_t trunk2_heads_bf16(const TrunkArgs& a, const HeadsFusedArgs& h, const Pac
     return SPNERF_OK;
 }
 
-#else   // product build: the two-workgroup trunk is not compiled
-bool trunk2_supported(const TrunkArgs&, bool) { return false; }
-int32_t trunk2_bf16(const TrunkArgs&, hipStream_t, bool, double, double) {
-    SPN_ARG(false, "trunk2_bf16: the two-workgroup trunk is an ablation-build kernel (-DSPN_ABLATIONS)");
-    return SPNERF_OK;
-}
-bool trunk2_heads_ok(const TrunkArgs&) { return false; }
-int32_t trunk2_heads_bf16(const TrunkArgs&, const HeadsFusedArgs&, const PackedOffs&, hipStream_t, double, double) {
-    SPN_ARG(false, "trunk2_heads_bf16: the two-workgroup trunk is an ablation-build kernel (-DSPN_ABLATIONS)");
-    return SPNERF_OK;
-}
-#endif  // SPN_ABLATIONS
-
 }  // namespace spn
 
 // resident workgroups per CU of the 64-point tiling (profiling aid: 2 expected; -1 in the product
 // build, which does not compile that kernel)
 extern "C" int32_t spnerf_debug_trunk2_occupancy(int32_t save) {
     int n = -1;
-#ifndef SPN_ABLATIONS
-    (void)save;
-    return n;
-#else
     const void* f = save ? (const void*)spn::k_trunk2_bf16<64, false, true, false> : (const void*)spn::k_trunk2_bf16<64, true, false, false>;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, spn::T2Geo<64>::NT, 0) != hipSuccess) return -1;
     return n;
-#endif
 }

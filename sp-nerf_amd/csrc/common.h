@@ -45,7 +45,8 @@ int num_cus();
 // launch never uses more splits than that (split_cus: the device's CUs, capped at kLayoutCus)
 constexpr int kLayoutCus = 256;
 // Profiling-ablation arguments of the kernels (dbg, nt) vary only in a -DSPN_ABLATIONS build; the
-// product build folds them to their defaults, so no runtime flag branches a hot loop
+// product build folds them to their defaults, so no runtime flag branches a hot loop.  The kernels
+// and launch code that exist only in that build are in csrc/ablations/.
 #ifdef SPN_ABLATIONS
 constexpr bool kAblBuild = true;
 #else

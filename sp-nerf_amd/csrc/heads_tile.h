@@ -1,6 +1,7 @@
 // The fused inference heads' per-tile computation (models/spnerf.py:332-367), shared by the
 // heads kernel (k_heads_bf16, heads_bf16.hip: H_L staged from HBM) and the fused trunk + heads
-// kernel (k_trunk2_bf16 with HEADS, trunk2_bf16.hip: H_L is the trunk's last LDS image).  What
+// kernels (k_trunk_bf16 with kVarHeads, trunk_bf16.hip, and the ablation build's k_trunk2_bf16 with
+// HEADS, ablations/trunk2_bf16.hip: H_L is the trunk's last LDS image).  What
 // each layer computes and why: heads_bf16.hip.
 #pragma once
 #include <algorithm>

@@ -7,7 +7,8 @@ namespace spn {
 
 constexpr int kTrunkMaxL = 16;
 // The trunk kernels' nt (cache policy of the copy-outs) and dbg (profiling ablations) arguments
-// vary only in a -DSPN_ABLATIONS build; the product build folds them to the product defaults, so
+// vary only in a -DSPN_ABLATIONS build (its kernels and launch code: csrc/ablations/); the product
+// build folds them to the product defaults, so
 // no store or copy-out sits behind a runtime branch (a branch around a store made hipcc's later
 // vmcnt waits conservative: they then waited for the stores as well)
 constexpr bool kTrunkAbl = kAblBuild;
@@ -274,7 +275,8 @@ int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes)
 // the launch trunk_bf16 would make for a (saving) computes the σ rows (TrunkArgs::sig_hsave)
 bool trunk_sigma_ok(const TrunkArgs& a, bool save);
 extern int g_trunk_sigma;  // option trunk_sigma
-// the two-workgroups-per-CU tiling (trunk2_bf16.hip): D stored from the registers, 76 KB of LDS
+// the two-workgroups-per-CU tiling (ablations/trunk2_bf16.hip, ablation build only; the product's
+// stubs are at the end of trunk_bf16.hip): D stored from the registers, 76 KB of LDS
 extern int g_trunk2;       // 0 = off, 1 = saving (training) launches, 2 = every launch
 extern int g_trunk2_tile;  // 64 or 128 points per tile
 bool trunk2_supported(const TrunkArgs& a, bool save);

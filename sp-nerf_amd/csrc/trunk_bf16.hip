@@ -25,7 +25,7 @@
 // Tilings:
 //  * TMt = 128, inference (nothing saved but the last layer's H): 148 KB of LDS, 4 B fragments
 //    per weight fragment (32 B/clk/CU of L2 weight traffic at the MFMA peak);
-//  * TMt = 128, training (the saving instance, VAR 2048: H_i and D_i of every layer saved for the
+//  * TMt = 128, training (the saving instance, VAR kVarSaving: H_i and D_i of every layer saved for the
 //    backward): H drains from the image behind the next layer's k-loop.  D = cos of the layers the
 //    dX chain reads leaves tile-ordered (trunk.h dtile_off, option fused_bwd 2) straight from the
 //    accumulators in ONE epilogue pass (epilogue_dt: sin and cos of the same r; a wave-wide 16-B
@@ -33,7 +33,12 @@
 //    off a 64-point boundary) takes two passes: cos into the image, each wave copying out its own
 //    columns, then sin over it;
 //  * TMt = 64 (option trunk_tile 64, and the saved-Z ablation path): the H and D images (64 KB
-//    each) both drain behind the next layer's k-loop; twice the weight traffic per point.
+//    each) both drain behind the next layer's k-loop; twice the weight traffic per point.  The
+//    product's instance is VAR kVarDReg: D leaves from the accumulators instead of a D image;
+//  * TMt = 128, inference with the fused heads (VAR kVarHeads, kVarHeads | kVarHeads2 for more
+//    than four semantic classes): the heads run on the last layer's image, H_L never leaves the chip.
+// (The kVar* bits of VAR are named at k_trunk_bf16; the ablation build's profiling instances are
+// launched from ablations/launch_trunk_bf16.inc.)
 #include <algorithm>
 #include <type_traits>
 
@@ -66,7 +71,7 @@ int g_trunk_tile = 0;  // 0 = 128 (64 when saving Z, zsave); 64 / 128 force a ti
 int g_trunk_nt = 1;
 int g_trunk_var = 0;  // profiling ablations of the 128-point tiling (k_trunk_bf16 VAR)
 int g_trunk_dreg = 1;  // 64-point training tiles: D = cos leaves from the accumulators in the epilogue
-                       // (VAR 512) instead of through the D image behind the next k-loop.  The same
+                       // (VAR kVarDReg) instead of through the D image behind the next k-loop.  The same
                        // epilogue on 128-point training tiles (no D image needed: 148 KB of LDS)
                        // measured 3.65 ms per 524 288 points against 2.96 (64) and 3.13 (128 with the
                        // two-barrier cos pass): 128 KB of D stores per epilogue hold up the refills
@@ -98,41 +103,54 @@ __device__ __forceinline__ int act_off(int row, int ch) { return row * 1024 + ((
 // lane group on distinct 16-B slots of the bank row
 __device__ __forceinline__ int x0_rel(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
 
-// VAR (TMt = 128 only): 0 = the kernel; profiling ablations (outputs invalid; option trunk_var),
-// bits: 16 = no MFMAs in the main k-loop, 32 = no sine in the epilogue, 64 = no weight refills
-// in the k-loop, 128 = no image (B) reads in the k-loop, 256 = no epilogue (464: all of them)
-// HEADS (VAR 4096; inference, TMt = 128, option trunk_heads 2): the fused heads (heads_tile.h) run
+// VAR: a mask of the bits below, 0 = the plain kernel.  The product's instances:
+constexpr int kVarDReg = 512;      // 64-point tiles: D from the registers (see epilogue_dreg)
+constexpr int kVarSaving = 2048;   // the saving (training) launches of the 128-point tiling
+constexpr int kVarHeads = 4096;    // the fused heads on the last layer's image (HEADS below)
+constexpr int kVarHeads2 = 16384;  // with kVarHeads: two class groups
+// Profiling ablations (outputs invalid; option trunk_var, launched only by the ablation build):
+constexpr int kVarNoMfma = 16;     // no MFMAs in the main k-loop
+constexpr int kVarNoSin = 32;      // no sine in the epilogue
+constexpr int kVarNoW = 64;        // no weight refills in the k-loop
+constexpr int kVarNoB = 128;       // no image (B) reads in the k-loop
+constexpr int kVarNoEpi = 256;     // no epilogue (option trunk_var 464: this with NoMfma, NoW and NoB)
+constexpr int kVarNoPe = 8192;     // the inline encoding's math skipped
+// HEADS (VAR kVarHeads; inference, TMt = 128, option trunk_heads 2): the fused heads (heads_tile.h) run
 // on the last layer's LDS image, so H_L never leaves the chip; their output staging is 8 KB beyond
 // the trunk's LDS, their partials overlay the PE tile (restaged by the next tile), and the weight
 // ring is primed per tile instead of running on through the heads.  The heads' arguments are read
 // per tile through an opaque kernarg pointer (not hoisted into registers live through the layers).
-// VAR 4096 | 16384: the heads with two groups of four semantic classes (4 < C <= 8), their own
+// VAR kVarHeads | kVarHeads2: the heads with two groups of four semantic classes (4 < C <= 8), their own
 // instance so that the one-group kernel keeps its registers.
+// (The argument type spells kVarHeads as 4096: this dependent expression is mangled into the kernel's
+// symbol, and the profiles and tools know the kernels by those names.)
+static_assert(kVarHeads == 4096, "k_trunk_bf16's argument type");
 template <int TMt, int VAR = 0>
 __global__ __launch_bounds__(512) void k_trunk_bf16(std::conditional_t<(VAR & 4096) != 0, TrunkHeadsArgs, TrunkArgs> g,
                                                     int ntiles) {
     using Geo = TrunkGeo<TMt>;
     constexpr int NJ = Geo::NJ, IMG = Geo::IMG, CPT = Geo::CPT;
     constexpr int TPD = Geo::TPD;
-    constexpr bool HEADS = (VAR & 4096) != 0;
-    constexpr int HNG = (VAR & 16384) ? 2 : 1;  // the heads' class groups
-    static_assert(!(VAR & 16384) || HEADS, "class groups: the fused heads' instances");
+    constexpr bool HEADS = (VAR & kVarHeads) != 0;
+    constexpr int HNG = (VAR & kVarHeads2) ? 2 : 1;  // the heads' class groups
+    static_assert(!(VAR & kVarHeads2) || HEADS, "class groups: the fused heads' instances");
     static_assert(!HEADS || (TMt == 128 && Geo::BIAS_OFF - Geo::X0_OFF >= hd::PART_BYTES &&
                              Geo::LDS + hd::OST_BYTES <= 160 * 1024), "the fused heads: 128-point tiles, LDS");
-    constexpr bool NOMF = VAR & 16, NOSIN = VAR & 32, NOW = VAR & 64, NOB = VAR & 128, NOEPI = VAR & 256;
-    constexpr bool NOPE = VAR & 8192;  // ablation (outputs invalid): the inline encoding's math skipped
-    constexpr bool DREG = Geo::DIMG && (VAR & 512);  // D from the registers (see epilogue_dreg)
-    // (VAR 2048: the saving launches of the 128-point tiling as their own instance — the same code,
+    constexpr bool NOMF = VAR & kVarNoMfma, NOSIN = VAR & kVarNoSin, NOW = VAR & kVarNoW, NOB = VAR & kVarNoB,
+                   NOEPI = VAR & kVarNoEpi;
+    constexpr bool NOPE = VAR & kVarNoPe;  // ablation (outputs invalid): the inline encoding's math skipped
+    constexpr bool DREG = Geo::DIMG && (VAR & kVarDReg);  // D from the registers (see epilogue_dreg)
+    // (kVarSaving: the saving launches of the 128-point tiling as their own instance — the same code,
     // so rocprof tells the training launches from the inference ones by name)
-    static_assert(!(VAR & 2048) || TMt == 128, "the 128-point training instance");
+    static_assert(!(VAR & kVarSaving) || TMt == 128, "the 128-point training instance");
     constexpr bool SRB = !HEADS;  // per-ray rows staged in LDS (the fused heads' kernel has no room)
-    constexpr bool SAVING = (VAR & 2048) != 0;  // the 128-point training instance (every layer saved)
+    constexpr bool SAVING = (VAR & kVarSaving) != 0;  // the 128-point training instance (every layer saved)
     __shared__ __attribute__((aligned(16))) char smem[Geo::LDS + (HEADS ? hd::OST_BYTES : Geo::SRB_BYTES)];
     float* srb = reinterpret_cast<float*>(smem + Geo::LDS);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r32 = lane & 31, h = lane >> 5;
     // product: the H copy-outs non-temporal (g_trunk_nt's default, bit 1; the fused-heads launch
     // copies nothing out and passes 0), the register-D stores not (bit 2)
-    constexpr int kNtDefault = (VAR & 4096) ? 0 : 1;
+    constexpr int kNtDefault = (VAR & kVarHeads) ? 0 : 1;
     const int gnt = kTrunkAbl ? g.nt : kNtDefault;
     const int gdbg = kTrunkAbl ? g.dbg : 0;
     float* sbias = reinterpret_cast<float*>(smem + Geo::BIAS_OFF);
@@ -1376,8 +1394,8 @@ int32_t trunk1_heads_bf16(const TrunkArgs& a, const HeadsFusedArgs& h, const Pac
     ad.hk = k;
     ProfScope prof("trunk_heads_bf16", s, flop, bytes);
     const dim3 grid(std::min(ntiles, num_cus())), block(512);
-    if (h.C > 4) hipLaunchKernelGGL((k_trunk_bf16<128, 4096 | 16384>), grid, block, 0, s, ad, ntiles);
-    else hipLaunchKernelGGL((k_trunk_bf16<128, 4096>), grid, block, 0, s, ad, ntiles);
+    if (h.C > 4) hipLaunchKernelGGL((k_trunk_bf16<128, kVarHeads | kVarHeads2>), grid, block, 0, s, ad, ntiles);
+    else hipLaunchKernelGGL((k_trunk_bf16<128, kVarHeads>), grid, block, 0, s, ad, ntiles);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -1388,6 +1406,9 @@ bool trunk_dtile_ok(const TrunkArgs& a) {
     return save && !a.zround && trunk_tile(true) == 128 && g_trunk_var == 0 && (a.X0b_out || !trunk2_supported(a, true));
 }
 
+#ifdef SPN_ABLATIONS
+#include "ablations/launch_trunk_bf16.inc"
+#endif
 int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes) {
     SPN_ARG(a.P >= 0 && a.S > 0, "trunk_bf16: bad sizes");
     SPN_ARG(trunk_bf16_supported(TW, a.L, a.skip, a.K0p), "trunk_bf16: unsupported shape L=%d skip=%d K0p=%d", a.L,
@@ -1414,32 +1435,39 @@ int32_t trunk_bf16(const TrunkArgs& a, hipStream_t s, double flop, double bytes)
     // H and D of every layer out) is not the inference launches' (MFMA-bound)
     ProfScope prof(save ? "trunk_bf16_train" : "trunk_bf16", s, flop, bytes);
     const dim3 grid(std::min(ntiles, num_cus())), block(512);
-    bool done = false;
 #ifdef SPN_ABLATIONS
-    // profiling ablations (outputs invalid) and the measured-slower 64-point tiling without the
-    // register-D epilogue: compiled only into -DSPN_ABLATIONS builds
-    done = true;
-    if (tm == 64 && g_trunk_dreg && g_trunk_var == 32)  // ablation: no sin / cos in the epilogue
-        hipLaunchKernelGGL((k_trunk_bf16<64, 544>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 64 && g_trunk_dreg && g_trunk_var == 256)  // ablation: no epilogue at all
-        hipLaunchKernelGGL((k_trunk_bf16<64, 768>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 64 && !g_trunk_dreg) hipLaunchKernelGGL(k_trunk_bf16<64>, grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 16) hipLaunchKernelGGL((k_trunk_bf16<128, 16>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 32) hipLaunchKernelGGL((k_trunk_bf16<128, 32>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 64) hipLaunchKernelGGL((k_trunk_bf16<128, 64>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 128) hipLaunchKernelGGL((k_trunk_bf16<128, 128>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 256) hipLaunchKernelGGL((k_trunk_bf16<128, 256>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && g_trunk_var == 464) hipLaunchKernelGGL((k_trunk_bf16<128, 464>), grid, block, 0, s, ad, ntiles);
-    else if (tm == 128 && save && g_trunk_var == 8192) hipLaunchKernelGGL((k_trunk_bf16<128, 2048 | 8192>), grid, block, 0, s, ad, ntiles);
-    else done = false;
+    if (!abl_launch_trunk_bf16(tm, save, grid, block, s, ad, ntiles))
 #endif
-    if (!done) {
-        if (tm == 64) hipLaunchKernelGGL((k_trunk_bf16<64, 512>), grid, block, 0, s, ad, ntiles);
-        else if (save) hipLaunchKernelGGL((k_trunk_bf16<128, 2048>), grid, block, 0, s, ad, ntiles);
-        else hipLaunchKernelGGL((k_trunk_bf16<128, 0>), grid, block, 0, s, ad, ntiles);
+    {
+        if (tm == 64) hipLaunchKernelGGL((k_trunk_bf16<64, kVarDReg>), grid, block, 0, s, ad, ntiles);
+        else if (save) hipLaunchKernelGGL((k_trunk_bf16<128, kVarSaving>), grid, block, 0, s, ad, ntiles);
+        else hipLaunchKernelGGL(k_trunk_bf16<128>, grid, block, 0, s, ad, ntiles);
     }
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
 
 }  // namespace spn
+
+#ifndef SPN_ABLATIONS
+// The two-workgroup trunk (ablations/trunk2_bf16.hip, measured slower than k_trunk_bf16) is not
+// compiled into the product build, which keeps the option variables and these stubs.
+namespace spn {
+int g_trunk2 = 0;
+int g_trunk2_tile = 128;
+int g_trunk_heads = 2;
+bool trunk2_supported(const TrunkArgs&, bool) { return false; }
+int32_t trunk2_bf16(const TrunkArgs&, hipStream_t, bool, double, double) {
+    SPN_ARG(false, "trunk2_bf16: the two-workgroup trunk is an ablation-build kernel (-DSPN_ABLATIONS)");
+    return SPNERF_OK;
+}
+bool trunk2_heads_ok(const TrunkArgs&) { return false; }
+int32_t trunk2_heads_bf16(const TrunkArgs&, const HeadsFusedArgs&, const PackedOffs&, hipStream_t, double, double) {
+    SPN_ARG(false, "trunk2_heads_bf16: the two-workgroup trunk is an ablation-build kernel (-DSPN_ABLATIONS)");
+    return SPNERF_OK;
+}
+}  // namespace spn
+
+// resident workgroups per CU of the two-workgroup trunk's 64-point tiling: -1, the kernel is not compiled
+extern "C" int32_t spnerf_debug_trunk2_occupancy(int32_t) { return -1; }
+#endif

@@ -19,7 +19,7 @@ from .rng import PhiloxRandom, ReplayRandom, TorchRandom, current_random_source,
 from .spnerf import (SPNeRF, Mapping, Siren, first_layer_sine_init, inference, inference_rays, run_mlp,  # noqa: F401
                      sine_init)
 from . import view  # noqa: F401  (whole views: image products and the validation scores on the GPU)
-from .view import render_image, view_metrics  # noqa: F401
+from .view import render_image, view_loss, view_metrics  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

@@ -27,6 +27,8 @@ from .perceptual import LpipsWeights, lpips  # noqa: F401
 from . import losses  # noqa: F401  (modules/metrics.py, and the fused training losses)
 from .losses import FusedRenderLoss, FusedTrainLoss  # noqa: F401
 from . import dataset  # noqa: F401  (depth priors, semantic labels and scene.loc: satellite_scene.py on the GPU)
+from . import train  # noqa: F401  (main.py's training step and schedule: one HIP-graph replay per step)
+from .train import EpochPlan, Trainer, make_plan  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -1,0 +1,62 @@
+"""ctypes structs and signatures of the training-step exports (include/spnerf_amd_train.h), applied
+to the same libspnerf_amd.so handle as ``_lib.SIGNATURES``; errors come back through ``_lib.check``."""
+from __future__ import annotations
+
+import ctypes
+from ctypes import POINTER, c_double, c_float, c_int32, c_int64, c_void_p
+
+from . import _lib
+
+SPNERF_TRAIN_ABI_VERSION = 1
+
+ERR_PAST_END = 1
+ERR_BATCH = 2
+
+
+class StepScalars(ctypes.Structure):
+    """spnerf_train_step_scalars: one step's row of the epoch plan."""
+    _fields_ = [("noise_std", c_float), ("lr", c_float), ("adam_step_size", c_float), ("adam_bc2_sqrt", c_float),
+                ("step", c_int64)]
+
+
+class TrainState(ctypes.Structure):
+    """spnerf_train_state: the device-resident description of the uploaded plan."""
+    _fields_ = [("cursor", c_int64), ("n_steps", c_int64), ("B", c_int64), ("error", c_int64)]
+
+
+# name → (restype, argtypes); the exact export list of include/spnerf_amd_train.h
+SIGNATURES = {
+    "spnerf_train_abi_version": (c_int32, []),
+    "spnerf_train_step_begin": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "spnerf_adam_step_dev": (c_int32, [c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                       POINTER(c_void_p), POINTER(c_int64), c_void_p, c_double, c_double, c_double,
+                                       c_void_p]),
+    "spnerf_composite_forward_dev": (c_int32, [c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                               c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               POINTER(_lib.Rng), c_void_p]),
+    "spnerf_composite_backward_dev": (c_int32, [c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                                c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, POINTER(_lib.Rng), c_void_p]),
+}
+
+_bound = False
+
+
+def lib():
+    """The library handle of ``_lib.lib()`` with the training-step signatures applied (once).  A
+    library without these exports is an error: there is no fallback."""
+    global _bound
+    handle = _lib.lib()
+    if not _bound:
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:
+                raise _lib.SpnerfError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
+                                       "(`make -C sp-nerf_amd`)") from None
+            fn.restype = res
+            fn.argtypes = args
+        if handle.spnerf_train_abi_version() != SPNERF_TRAIN_ABI_VERSION:
+            raise _lib.SpnerfError("libspnerf_amd.so: training-step ABI version mismatch, rebuild it")
+        _bound = True
+    return handle

@@ -7,6 +7,8 @@
 
 #include "common.h"
 
+#include "../../include/spnerf_amd_train.h"
+
 namespace spn {
 
 constexpr int kAdamSeg = 48;           // tensors per launch (kernel-argument budget)
@@ -28,15 +30,29 @@ struct AdamArgs {
 
 // torch's single-tensor Adam arithmetic (torch/optim/adam.py _single_tensor_adam):
 // m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g; p -= step_size * m / (sqrt(v)/sqrt(bc2) + eps)
-__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamArgs& a) {
+// step_size and bc2_sqrt come from the arguments (k_adam) or from the step's device-resident
+// scalars (k_adam_dev, spnerf_adam_step_dev): one arithmetic for both.  The roundings are spelled
+// out instead of being left to the compiler's contraction, which decides by what else shares the
+// function (a product is fused into the following add exactly where fmaf stands; the pragma is
+// honoured under -ffp-contract=fast-honor-pragmas, see the Makefile).  VEC, the 16-byte path, fuses
+// v·β2 into the sum and rounds (w2·g)·g; the element path rounds v·β2 and fuses the other product.
+// The asymmetry has no merit of its own: it is what the compiler chose for k_adam's two paths
+// before this function was shared, written down so that spnerf_adam_step's results stay what they
+// were.
+template <bool VEC>
+__device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamArgs& a, float step_size,
+                                      float bc2_sqrt) {
+#pragma clang fp contract(off)
     const float w = a.w1;
-    m = w < 0.5f ? m + w * (g - m) : g - (g - m) * (1.f - w);
-    v = v * a.beta2 + (a.w2 * g) * g;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p = p + (-a.step_size) * (m / denom);
+    const float d = g - m;
+    m = w < 0.5f ? __builtin_fmaf(w, d, m) : __builtin_fmaf(-(1.f - w), d, g);
+    const float gg = a.w2 * g;
+    v = VEC ? __builtin_fmaf(v, a.beta2, gg * g) : __builtin_fmaf(gg, g, v * a.beta2);
+    const float denom = sqrtf(v) / bc2_sqrt + a.eps;
+    p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
-__global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
+__device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, float bc2_sqrt) {
     typedef const __attribute__((address_space(4))) AdamArgs* KArgs;
     const KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     const int64_t b = blockIdx.x;
@@ -58,7 +74,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pe = p[e], me = m[e], ve = v[e];
-                adam1(pe, g[e], me, ve, a);
+                adam1<true>(pe, g[e], me, ve, a, step_size, bc2_sqrt);
                 p[e] = pe;
                 m[e] = me;
                 v[e] = ve;
@@ -69,13 +85,39 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
         } else {
             for (int64_t j = i; j < i + 4 && j < sg.n; ++j) {
                 float p = sg.p[j], m = sg.m[j], v = sg.v[j];
-                adam1(p, sg.g[j], m, v, a);
+                adam1<false>(p, sg.g[j], m, v, a, step_size, bc2_sqrt);
                 sg.p[j] = p;
                 sg.m[j] = m;
                 sg.v[j] = v;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_adam(AdamArgs a) { adam_block(a, a.step_size, a.bc2_sqrt); }
+
+// the kernel-argument block is the first argument in both kernels (adam_block reads the tensor
+// table through the kernarg segment pointer)
+__global__ __launch_bounds__(256) void k_adam_dev(AdamArgs a, const spnerf_train_step_scalars* cur) {
+    adam_block(a, cur->adam_step_size, cur->adam_bc2_sqrt);
+}
+
+// the tensor table of one launch from entry i of the lists on: up to kAdamSeg non-empty tensors
+static int32_t adam_fill(AdamArgs& a, int& i, int32_t n, void* const* params, const void* const* grads,
+                         void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel, int64_t* blocks_out) {
+    int64_t blocks = 0;
+    for (; i < n && a.nseg < kAdamSeg; ++i) {
+        SPN_ARG(numel[i] >= 0, "adam_step: tensor %d has negative size", i);
+        if (numel[i] == 0) continue;
+        a.s[a.nseg] = AdamSeg{(float*)params[i], (const float*)grads[i], (float*)exp_avg[i], (float*)exp_avg_sq[i],
+                              numel[i]};
+        a.first_block[a.nseg] = blocks;
+        blocks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+        ++a.nseg;
+    }
+    a.first_block[a.nseg] = blocks;
+    *blocks_out = blocks;
+    return SPNERF_OK;
 }
 
 }  // namespace spn
@@ -99,20 +141,37 @@ extern "C" int32_t spnerf_adam_step(int32_t n, void* const* params, const void* 
         a.step_size = (float)(lr / bc1);
         a.bc2_sqrt = (float)std::sqrt(bc2);
         int64_t blocks = 0;
-        for (; i < n && a.nseg < kAdamSeg; ++i) {
-            SPN_ARG(numel[i] >= 0, "adam_step: tensor %d has negative size", i);
-            if (numel[i] == 0) continue;
-            a.s[a.nseg] = AdamSeg{(float*)params[i], (const float*)grads[i], (float*)exp_avg[i], (float*)exp_avg_sq[i],
-                                  numel[i]};
-            a.first_block[a.nseg] = blocks;
-            blocks += (numel[i] + kAdamChunk - 1) / kAdamChunk;
-            ++a.nseg;
-        }
-        a.first_block[a.nseg] = blocks;
+        SPN_TRY(adam_fill(a, i, n, params, grads, exp_avg, exp_avg_sq, numel, &blocks));
         if (blocks == 0) continue;
         SPN_ARG(blocks < (1ll << 31), "adam_step: too many elements");
         ProfScope prof("adam", s, 0.0, 0.0);
         hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(256), 0, s, a);
+        SPN_HIP(hipGetLastError());
+    }
+    return SPNERF_OK;
+}
+
+extern "C" int32_t spnerf_adam_step_dev(int32_t n, void* const* params, const void* const* grads, void* const* exp_avg,
+                                        void* const* exp_avg_sq, const int64_t* numel,
+                                        const spnerf_train_step_scalars* cur, double beta1, double beta2, double eps,
+                                        void* stream) {
+    SPN_ARG(n >= 0 && (n == 0 || (params && grads && exp_avg && exp_avg_sq && numel)), "adam_step_dev: bad lists");
+    SPN_ARG(cur, "adam_step_dev: NULL step scalars");
+    SPN_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps > 0.0,
+            "adam_step_dev: bad hyper-parameters");
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < n;) {
+        AdamArgs a{};
+        a.w1 = (float)(1.0 - beta1);
+        a.beta2 = (float)beta2;
+        a.w2 = (float)(1.0 - beta2);
+        a.eps = (float)eps;
+        int64_t blocks = 0;
+        SPN_TRY(adam_fill(a, i, n, params, grads, exp_avg, exp_avg_sq, numel, &blocks));
+        if (blocks == 0) continue;
+        SPN_ARG(blocks < (1ll << 31), "adam_step_dev: too many elements");
+        ProfScope prof("adam", s, 0.0, 0.0);
+        hipLaunchKernelGGL(k_adam_dev, dim3((unsigned)blocks), dim3(256), 0, s, a, cur);
         SPN_HIP(hipGetLastError());
     }
     return SPNERF_OK;

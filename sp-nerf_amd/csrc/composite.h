@@ -20,6 +20,9 @@ struct CompArgs {
     // its gradient into d_out's sun column (backward) — the solar pass's sun_sc (rendering.py:177)
     float* sun_out;
     const float* g_sun;
+    // spnerf_composite_*_dev: noise_std read from the device (a captured training step's schedule,
+    // include/spnerf_amd_train.h); null on every other path, which reads the argument above
+    const float* noise_std_dev;
 };
 
 __device__ __forceinline__ float relu_t(float x) { return x != x ? x : (x > 0.f ? x : 0.f); }
@@ -34,6 +37,7 @@ struct RayState {
 template <int EPL>
 __device__ __forceinline__ void march(const CompArgs& a, int64_t ray, int lane, const float* rows, RayState<EPL>& st) {
     const int S = a.S;
+    const float noise_std = a.noise_std_dev ? *a.noise_std_dev : a.noise_std;
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
         const int e = lane * EPL + j;
@@ -46,8 +50,8 @@ __device__ __forceinline__ void march(const CompArgs& a, int64_t ray, int lane, 
         if (e < S) {
             const int64_t p = ray * S + e;
             float sg = rows[e * a.NO + 3];
-            if (a.noise) sg = sg + a.noise[p] * a.noise_std;
-            else if (a.rng.state) sg = sg + rng_normal(a.rng, ray, e) * a.noise_std;
+            if (a.noise) sg = sg + a.noise[p] * noise_std;
+            else if (a.rng.state) sg = sg + rng_normal(a.rng, ray, e) * noise_std;
             const float zn = j + 1 < EPL ? st.z[j + 1] : zn0;
             const float dl = e == S - 1 ? 1e10f : zn - st.z[j];
             const float r = relu_t(sg);

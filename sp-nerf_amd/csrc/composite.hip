@@ -13,6 +13,8 @@
 // clamp's inclusive pass-through mask, relu's result>0 mask, mean's division by S.
 #include "composite.h"
 
+#include "../../include/spnerf_amd_train.h"
+
 namespace spn {
 
 template <int EPL>
@@ -265,6 +267,53 @@ extern "C" int32_t spnerf_composite_backward(int64_t n_rays, int32_t n_samples, 
     a.d_out = d_out;
     if (flags & SPNERF_COMP_SUN_COLUMN) {
         SPN_ARG(wo, "composite_backward: SPNERF_COMP_SUN_COLUMN needs SPNERF_COMP_WEIGHTS_ONLY");
+        a.g_sun = g_rgb;
+        a.g_rgb = nullptr;
+    }
+    return run_comp(a, false, (hipStream_t)stream);
+}
+
+// ---- noise_std on the device (include/spnerf_amd_train.h): the same kernels, CompArgs::noise_std_dev
+// set.  The draw cannot be skipped on the host at *noise_std == 0: it is made and multiplied.
+
+extern "C" int32_t spnerf_composite_forward_dev(int64_t n_rays, int32_t n_samples, const float* z, const float* out,
+                                                int32_t n_out, const float* noise, const float* noise_std,
+                                                int32_t sem_col, int32_t n_sem, int32_t flags, float* rgb, float* depth,
+                                                float* weights, float* transparency, float* sem_logits,
+                                                const spnerf_rng* rng, void* stream) {
+    const bool wo = flags & SPNERF_COMP_WEIGHTS_ONLY;
+    SPN_ARG(z && out && depth && weights && transparency && noise_std, "composite_forward_dev: NULL pointer");
+    SPN_ARG(wo || rgb, "composite_forward_dev: rgb is NULL");
+    SPN_ARG(wo || n_sem == 0 || sem_logits, "composite_forward_dev: sem_logits is NULL");
+    CompArgs a{};
+    a.B = n_rays; a.S = n_samples; a.NO = n_out; a.sem_col = sem_col; a.n_sem = wo ? 0 : n_sem; a.weights_only = wo;
+    a.z = z; a.out = out; a.noise = noise; a.noise_std_dev = noise_std;
+    if (!noise && rng) a.rng = *rng;
+    a.rgb = rgb; a.depth = depth; a.w = weights; a.T = transparency; a.sem = sem_logits;
+    if (flags & SPNERF_COMP_SUN_COLUMN) {
+        SPN_ARG(wo && rgb, "composite_forward_dev: SPNERF_COMP_SUN_COLUMN needs SPNERF_COMP_WEIGHTS_ONLY and rgb");
+        a.sun_out = rgb;
+        a.rgb = nullptr;
+    }
+    return run_comp(a, true, (hipStream_t)stream);
+}
+
+extern "C" int32_t spnerf_composite_backward_dev(int64_t n_rays, int32_t n_samples, const float* z, const float* out,
+                                                 int32_t n_out, const float* noise, const float* noise_std,
+                                                 int32_t sem_col, int32_t n_sem, int32_t flags, const float* g_rgb,
+                                                 const float* g_depth, const float* g_weights,
+                                                 const float* g_transparency, const float* g_sem, float* d_out,
+                                                 const spnerf_rng* rng, void* stream) {
+    const bool wo = flags & SPNERF_COMP_WEIGHTS_ONLY;
+    SPN_ARG(z && out && d_out && noise_std, "composite_backward_dev: NULL pointer");
+    CompArgs a{};
+    a.B = n_rays; a.S = n_samples; a.NO = n_out; a.sem_col = sem_col; a.n_sem = wo ? 0 : n_sem; a.weights_only = wo;
+    a.z = z; a.out = out; a.noise = noise; a.noise_std_dev = noise_std;
+    if (!noise && rng) a.rng = *rng;
+    a.g_rgb = g_rgb; a.g_depth = g_depth; a.g_w = g_weights; a.g_T = g_transparency; a.g_sem = g_sem;
+    a.d_out = d_out;
+    if (flags & SPNERF_COMP_SUN_COLUMN) {
+        SPN_ARG(wo, "composite_backward_dev: SPNERF_COMP_SUN_COLUMN needs SPNERF_COMP_WEIGHTS_ONLY");
         a.g_sun = g_rgb;
         a.g_rgb = nullptr;
     }

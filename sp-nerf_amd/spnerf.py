@@ -12,7 +12,9 @@ csrc/composite.hip.  Nothing here has a CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import threading
 from typing import Optional
 
 import numpy as np
@@ -595,7 +597,10 @@ def max_points_per_call(model: SPNeRF) -> int:
 
 class _Composite(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, out, z, noise, noise_std, sem_col, n_sem, weights_only, rng=None, rng_keep=None, sun_col=False):
+    def forward(ctx, out, z, noise, noise_std, sem_col, n_sem, weights_only, rng=None, rng_keep=None, sun_col=False,
+                noise_std_dev=None):
+        """``noise_std_dev`` (a device tensor holding one float, see ``device_noise_std``): the
+        kernels read noise_std there and ``noise_std`` is ignored (spnerf_composite_*_dev)."""
         B, S = z.shape
         NO = out.shape[1]
         dev = out.device
@@ -609,12 +614,20 @@ class _Composite(torch.autograd.Function):
         depth = torch.empty(B, device=dev)
         w = torch.empty(B, S, device=dev)
         T = torch.empty(B, S, device=dev)
-        _lib.check(_lib.lib().spnerf_composite_forward(B, S, _lib.ptr(z), _lib.ptr(out), NO, _lib.ptr(noise),
-                                                       float(noise_std), sem_col, n_sem, f, _lib.ptr(rgb), _lib.ptr(depth),
-                                                       _lib.ptr(w), _lib.ptr(T), _lib.ptr(sem), _lib.rng_ref(rng),
-                                                       _lib.stream_of(out)), "composite_forward")
+        if noise_std_dev is not None:
+            from . import _train_lib
+            _lib.check(_train_lib.lib().spnerf_composite_forward_dev(
+                B, S, _lib.ptr(z), _lib.ptr(out), NO, _lib.ptr(noise), _lib.ptr(noise_std_dev), sem_col, n_sem, f,
+                _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(T), _lib.ptr(sem), _lib.rng_ref(rng),
+                _lib.stream_of(out)), "composite_forward_dev")
+        else:
+            _lib.check(_lib.lib().spnerf_composite_forward(B, S, _lib.ptr(z), _lib.ptr(out), NO, _lib.ptr(noise),
+                                                           float(noise_std), sem_col, n_sem, f, _lib.ptr(rgb),
+                                                           _lib.ptr(depth), _lib.ptr(w), _lib.ptr(T), _lib.ptr(sem),
+                                                           _lib.rng_ref(rng), _lib.stream_of(out)), "composite_forward")
         ctx.save_for_backward(out, z, noise)
         ctx.cfg = (float(noise_std), sem_col, n_sem, f)
+        ctx.noise_std_dev = noise_std_dev
         ctx.rng, ctx.rng_keep = rng, rng_keep   # the backward redraws the same on-device noise
         ctx.set_materialize_grads(False)
         return rgb, depth, w, T, sem
@@ -627,12 +640,40 @@ class _Composite(torch.autograd.Function):
         # contiguous copies stay bound to names until the library call has been issued
         g_rgb, g_depth, g_w, g_T, g_sem = (None if g is None else g.contiguous() for g in (g_rgb, g_depth, g_w, g_T, g_sem))
         d_out = torch.empty_like(out)
+        if ctx.noise_std_dev is not None:
+            from . import _train_lib
+            _lib.check(_train_lib.lib().spnerf_composite_backward_dev(
+                B, S, _lib.ptr(z), _lib.ptr(out), out.shape[1], _lib.ptr(noise), _lib.ptr(ctx.noise_std_dev), sem_col,
+                n_sem, f, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_w), _lib.ptr(g_T), _lib.ptr(g_sem),
+                _lib.ptr(d_out), _lib.rng_ref(ctx.rng), _lib.stream_of(out)), "composite_backward_dev")
+            return d_out, None, None, None, None, None, None, None, None, None, None
         _lib.check(_lib.lib().spnerf_composite_backward(B, S, _lib.ptr(z), _lib.ptr(out), out.shape[1], _lib.ptr(noise),
                                                         noise_std, sem_col, n_sem, f, _lib.ptr(g_rgb),
                                                         _lib.ptr(g_depth), _lib.ptr(g_w), _lib.ptr(g_T),
                                                         _lib.ptr(g_sem), _lib.ptr(d_out), _lib.rng_ref(ctx.rng),
                                                         _lib.stream_of(out)), "composite_backward")
-        return d_out, None, None, None, None, None, None, None, None, None
+        return d_out, None, None, None, None, None, None, None, None, None, None
+
+
+# Where the composites of the calling thread read noise_std: None = the ``noise_std`` argument (a
+# host float baked into the launch), or a device tensor of one float that the kernels read when
+# they run (spnerf_composite_*_dev) — the trainer's captured step, whose noise_std decays on the
+# device from replay to replay (train.Trainer).
+_noise_std_source = threading.local()
+
+
+@contextlib.contextmanager
+def device_noise_std(t: Optional[torch.Tensor]):
+    """Within the block every ``composite()`` of this thread reads noise_std from ``t`` (one fp32
+    on the device) and ignores its host argument.  Needs an on-device random source
+    (``PhiloxRandom``): whether ``t`` is 0 is not known on the host, so the draw is always made
+    in the kernel (and multiplied), never as a host-side tensor."""
+    prev = getattr(_noise_std_source, "t", None)
+    _noise_std_source.t = t
+    try:
+        yield t
+    finally:
+        _noise_std_source.t = prev
 
 
 def composite(model: SPNeRF, out: torch.Tensor, z: torch.Tensor, noise_std: float, weights_only=False, sun_col=False):
@@ -641,11 +682,16 @@ def composite(model: SPNeRF, out: torch.Tensor, z: torch.Tensor, noise_std: floa
     backward writes into d_out's sun column (the solar pass's sun_sc, rendering.py:177)."""
     B, S = z.shape
     key, keep = device_key(z.device)   # on-device σ noise: a slot per inference call, drawn or not
+    sem_col = 8 + (1 if model.beta else 0)
+    n_sem = model.num_sem_classes if model.sem else 0
+    ns_dev = getattr(_noise_std_source, "t", None)
+    if ns_dev is not None:
+        if key is None:
+            raise _lib.SpnerfError("device_noise_std needs a random source that draws on the device (PhiloxRandom)")
+        return _Composite.apply(out, z.contiguous(), None, 0.0, sem_col, n_sem, weights_only, key, keep, sun_col, ns_dev)
     noise = None if key is not None else current_random_source().noise((B, S), z.device, noise_std)   # spnerf.py:122
     if noise is not None:
         noise = noise.contiguous().float()
-    sem_col = 8 + (1 if model.beta else 0)
-    n_sem = model.num_sem_classes if model.sem else 0
     return _Composite.apply(out, z.contiguous(), noise, noise_std, sem_col, n_sem, weights_only,
                             key if noise_std != 0 else None, keep, sun_col)
 

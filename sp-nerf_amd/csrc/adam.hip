@@ -7,6 +7,7 @@
 
 #include "common.h"
 
+#include "../../include/spnerf_amd_dp.h"
 #include "../../include/spnerf_amd_train.h"
 
 namespace spn {
@@ -52,7 +53,18 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
     p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
-__device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, float bc2_sqrt) {
+// A gradient element of the scaled entry (spnerf_adam_step_dev_scaled): the product rounded to
+// float on its own, never contracted into adam1's g - m, so that scale = 2^-k gives the bits of a
+// gradient divided beforehand (subnormals included) and scale = 1 gives g itself.
+__device__ __forceinline__ float scaled_grad(float g, float scale) {
+#pragma clang fp contract(off)
+    return g * scale;
+}
+
+// SCALED: every gradient element goes through scaled_grad as it is loaded; otherwise `scale` is
+// not read and the code is what it was before the template parameter.
+template <bool SCALED>
+__device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, float bc2_sqrt, float scale = 1.f) {
     typedef const __attribute__((address_space(4))) AdamArgs* KArgs;
     const KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     const int64_t b = blockIdx.x;
@@ -74,7 +86,7 @@ __device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, f
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float pe = p[e], me = m[e], ve = v[e];
-                adam1<true>(pe, g[e], me, ve, a, step_size, bc2_sqrt);
+                adam1<true>(pe, SCALED ? scaled_grad(g[e], scale) : g[e], me, ve, a, step_size, bc2_sqrt);
                 p[e] = pe;
                 m[e] = me;
                 v[e] = ve;
@@ -85,7 +97,7 @@ __device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, f
         } else {
             for (int64_t j = i; j < i + 4 && j < sg.n; ++j) {
                 float p = sg.p[j], m = sg.m[j], v = sg.v[j];
-                adam1<false>(p, sg.g[j], m, v, a, step_size, bc2_sqrt);
+                adam1<false>(p, SCALED ? scaled_grad(sg.g[j], scale) : sg.g[j], m, v, a, step_size, bc2_sqrt);
                 sg.p[j] = p;
                 sg.m[j] = m;
                 sg.v[j] = v;
@@ -94,12 +106,16 @@ __device__ __forceinline__ void adam_block(const AdamArgs& a, float step_size, f
     }
 }
 
-__global__ __launch_bounds__(256) void k_adam(AdamArgs a) { adam_block(a, a.step_size, a.bc2_sqrt); }
+__global__ __launch_bounds__(256) void k_adam(AdamArgs a) { adam_block<false>(a, a.step_size, a.bc2_sqrt); }
 
-// the kernel-argument block is the first argument in both kernels (adam_block reads the tensor
+// the kernel-argument block is the first argument in every kernel (adam_block reads the tensor
 // table through the kernarg segment pointer)
 __global__ __launch_bounds__(256) void k_adam_dev(AdamArgs a, const spnerf_train_step_scalars* cur) {
-    adam_block(a, cur->adam_step_size, cur->adam_bc2_sqrt);
+    adam_block<false>(a, cur->adam_step_size, cur->adam_bc2_sqrt);
+}
+
+__global__ __launch_bounds__(256) void k_adam_dev_scaled(AdamArgs a, const spnerf_train_step_scalars* cur, float scale) {
+    adam_block<true>(a, cur->adam_step_size, cur->adam_bc2_sqrt, scale);
 }
 
 // the tensor table of one launch from entry i of the lists on: up to kAdamSeg non-empty tensors
@@ -151,14 +167,15 @@ extern "C" int32_t spnerf_adam_step(int32_t n, void* const* params, const void* 
     return SPNERF_OK;
 }
 
-extern "C" int32_t spnerf_adam_step_dev(int32_t n, void* const* params, const void* const* grads, void* const* exp_avg,
-                                        void* const* exp_avg_sq, const int64_t* numel,
-                                        const spnerf_train_step_scalars* cur, double beta1, double beta2, double eps,
-                                        void* stream) {
-    SPN_ARG(n >= 0 && (n == 0 || (params && grads && exp_avg && exp_avg_sq && numel)), "adam_step_dev: bad lists");
-    SPN_ARG(cur, "adam_step_dev: NULL step scalars");
-    SPN_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps > 0.0,
-            "adam_step_dev: bad hyper-parameters");
+// spnerf_adam_step_dev (scale == nullptr) and spnerf_adam_step_dev_scaled: one host path, two kernels
+static int32_t adam_step_dev(const char* what, int32_t n, void* const* params, const void* const* grads,
+                             void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
+                             const spnerf_train_step_scalars* cur, double beta1, double beta2, double eps,
+                             const float* scale, void* stream) {
+    SPN_ARG(n >= 0 && (n == 0 || (params && grads && exp_avg && exp_avg_sq && numel)), "%s: bad lists", what);
+    SPN_ARG(cur, "%s: NULL step scalars", what);
+    SPN_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps > 0.0, "%s: bad hyper-parameters", what);
+    SPN_ARG(!scale || (std::isfinite(*scale) && *scale > 0.f), "%s: grad_scale must be finite and > 0", what);
     hipStream_t s = (hipStream_t)stream;
     for (int i = 0; i < n;) {
         AdamArgs a{};
@@ -169,10 +186,27 @@ extern "C" int32_t spnerf_adam_step_dev(int32_t n, void* const* params, const vo
         int64_t blocks = 0;
         SPN_TRY(adam_fill(a, i, n, params, grads, exp_avg, exp_avg_sq, numel, &blocks));
         if (blocks == 0) continue;
-        SPN_ARG(blocks < (1ll << 31), "adam_step_dev: too many elements");
+        SPN_ARG(blocks < (1ll << 31), "%s: too many elements", what);
         ProfScope prof("adam", s, 0.0, 0.0);
-        hipLaunchKernelGGL(k_adam_dev, dim3((unsigned)blocks), dim3(256), 0, s, a, cur);
+        if (scale) hipLaunchKernelGGL(k_adam_dev_scaled, dim3((unsigned)blocks), dim3(256), 0, s, a, cur, *scale);
+        else hipLaunchKernelGGL(k_adam_dev, dim3((unsigned)blocks), dim3(256), 0, s, a, cur);
         SPN_HIP(hipGetLastError());
     }
     return SPNERF_OK;
+}
+
+extern "C" int32_t spnerf_adam_step_dev(int32_t n, void* const* params, const void* const* grads, void* const* exp_avg,
+                                        void* const* exp_avg_sq, const int64_t* numel,
+                                        const spnerf_train_step_scalars* cur, double beta1, double beta2, double eps,
+                                        void* stream) {
+    return adam_step_dev("adam_step_dev", n, params, grads, exp_avg, exp_avg_sq, numel, cur, beta1, beta2, eps, nullptr,
+                         stream);
+}
+
+extern "C" int32_t spnerf_adam_step_dev_scaled(int32_t n, void* const* params, const void* const* grads,
+                                               void* const* exp_avg, void* const* exp_avg_sq, const int64_t* numel,
+                                               const spnerf_train_step_scalars* cur, double beta1, double beta2,
+                                               double eps, float grad_scale, void* stream) {
+    return adam_step_dev("adam_step_dev_scaled", n, params, grads, exp_avg, exp_avg_sq, numel, cur, beta1, beta2, eps,
+                         &grad_scale, stream);
 }

@@ -192,26 +192,36 @@ class BatchGather:
         return self.out
 
 
-def allreduce_grads(params, world: int, group=None):
+def allreduce_grads(params, world: int, group=None, scale: bool = True, force: bool = False):
     """One flat all-reduce (SUM then /world) of every gradient.
 
     Parameters without a gradient stay without one (Adam skips them, as on one GPU).  Which
     parameters have gradients depends only on the model configuration and the render flags, so
-    the set is the same on every rank and the flat buffers line up."""
-    if world <= 1:
+    the set is the same on every rank and the flat buffers line up.  ``scale=False`` leaves the
+    SUM (the caller scales, e.g. inside Adam); ``force``: also with one rank (a rehearsal of the
+    collective on one GPU)."""
+    if world <= 1 and not force:
         return
     have = [p for p in params if p.grad is not None]
     if not have:
         return
+    scale = scale and world > 1
     grads = [p.grad for p in have]
     flat = _shared_flat(grads)
     if flat is not None:   # the .grads are consecutive views of one buffer (SPNeRF's flat gradient)
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-        flat.div_(world)
+        if scale:
+            flat.div_(world)
+        return
+    if len(grads) == 1 and grads[0].is_contiguous():   # one tensor: in place, no flatten and copy back
+        dist.all_reduce(grads[0], op=dist.ReduceOp.SUM, group=group)
+        if scale:
+            grads[0].div_(world)
         return
     flat = torch._utils._flatten_dense_tensors(grads)
     dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
-    flat.div_(world)
+    if scale:
+        flat.div_(world)
     for p, g in zip(have, torch._utils._unflatten_dense_tensors(flat, grads)):
         p.grad.copy_(g)
 
@@ -285,13 +295,15 @@ class GradBuckets:
                 self.works.append(dist.all_reduce(flat[lo:hi], op=dist.ReduceOp.SUM, group=self.group,
                                                   async_op=True))
 
-    def finish(self, flat: torch.Tensor, force: bool = False) -> None:
+    def finish(self, flat: torch.Tensor, force: bool = False, scale: bool = True) -> None:
+        """``scale=False`` leaves the SUM in ``flat`` (the trainer's Adam multiplies by 1/world as it
+        loads the gradient: spnerf_adam_step_dev_scaled), saving the pass that divides."""
         if self.world <= 1 and not force:
             return
         for w in self.works:
             w.wait()
         self.works = []
-        if self.world > 1:
+        if self.world > 1 and scale:
             flat.div_(self.world)
 
 

@@ -149,7 +149,7 @@ def _parameters(models):
 
 
 class Trainer:
-    """The reference's training loop on one GPU.
+    """The reference's training loop on one GPU, or data-parallel on N.
 
     ``models``: the ``{"coarse", ["fine"], ["t"]}`` dictionary ``render_rays`` takes; ``args``: the
     reference's ``Train_parser`` names (``lr``, ``batch_size``, ``max_train_steps``, ``noise_std``,
@@ -168,23 +168,56 @@ class Trainer:
     due; the previous epoch's error word is read then (one host sync per epoch).
 
     The batch is rendered in one ``render_rays`` call (``batch_size <= chunk``), so the guided
-    clamp's first ray is the batch's first ray."""
+    clamp's first ray is the batch's first ray.
+
+    Data parallelism (``world > 1``, one process per GPU inside a ``torch.distributed`` group, see
+    ``dp.init_from_env``): ``args.batch_size`` stays the GLOBAL batch B and each rank trains
+    ``b = B // world`` rays of it.  Every rank builds the same ``Schedule`` from the same seed, so
+    plan and permutation agree without a collective.  The step starts with ``spnerf_dp_step_begin``
+    (include/spnerf_amd_dp.h): the row, this rank's slice of the global batch, the global batch's
+    first ray's near / far (the guided clamp all ranks share) and the global batch's labels (the
+    CE's denominator) into fixed buffers; the draws are keyed by the global ray id
+    (``PhiloxRandom(ray_offset=rank·b)``).  The gradients are all-reduced (SUM) in ``dp.GradBuckets``
+    per SPNeRF plus one small all-reduce for parameters outside a flat buffer (the ``t`` embedding),
+    and ``spnerf_adam_step_dev_scaled`` multiplies by 1/world as it loads them: no pass divides.
+    ``collectives="graph"`` (nccl only) captures the bucket all-reduces behind the backward's marks
+    with the rest of the step — still one replay per step; ``"host"`` (gloo; any backend) ends the
+    graph with the backward and issues the all-reduces and Adam after each replay: a few host calls
+    more, no host sync of the trainer's; ``"auto"`` = ``"graph"`` for nccl, else ``"host"``.
+    ``world=1`` with an explicit ``group`` rehearses that machinery with one rank (identity
+    all-reduces, scale 1); ``world=1`` without a group is the single-GPU path.  ``rank`` is the
+    group's.  ``step()`` returns this rank's loss; ``global_loss(loss)`` all-reduces it."""
 
     def __init__(self, models, args, dataset_tensors, *, seed: int = 0, precision: str | None = None,
-                 graph: bool = True, world: int = 1, betas=(0.9, 0.999), eps: float = 1e-8):
+                 graph: bool = True, world: int = 1, rank: int = 0, group=None, collectives: str = "auto",
+                 betas=(0.9, 0.999), eps: float = 1e-8):
+        # what needs neither the library nor a device comes first
+        world, rank = int(world), int(rank)
+        if world < 1:
+            raise ValueError(f"Trainer: world = {world} < 1")
+        if int(args.batch_size) % world:
+            raise ValueError(f"Trainer: the global batch_size {int(args.batch_size)} does not divide over {world} ranks")
+        if collectives not in ("auto", "graph", "host"):
+            raise ValueError(f"Trainer: collectives must be 'auto', 'graph' or 'host', got {collectives!r}")
+        self.dp = world > 1 or group is not None      # the data-parallel machinery (one rank: a rehearsal)
+        self.world, self.group, self.collectives = world, group, None
+        if self.dp:
+            rank = self._join_group(world, rank, group, collectives)
+        elif rank != 0:
+            raise ValueError(f"Trainer: rank {rank} with world = 1")
+        self.rank = rank
         from . import _train_lib
         from .spnerf import SPNeRF
-        if world > 1:
-            raise NotImplementedError("Trainer: data parallelism (world > 1) is not part of the trainer yet")
         self._tl = _train_lib
         self.lib = _train_lib.lib()
         self.models = models
         self.args = a = types.SimpleNamespace(**vars(args))
         self.graph_mode = bool(graph)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
-        B = self.B = int(a.batch_size)
-        if B > int(getattr(a, "chunk", B)):
-            raise NotImplementedError(f"Trainer: batch_size {B} > chunk {a.chunk}: the batch is rendered in one call")
+        B = self.B = int(a.batch_size)          # the GLOBAL batch (the reference's batch_size)
+        b = self.b = B // world                 # this rank's rays per step
+        if b > int(getattr(a, "chunk", b)):
+            raise NotImplementedError(f"Trainer: batch_size {b} > chunk {a.chunk}: the batch is rendered in one call")
         self.fields = {k: dataset_tensors[k] for k in FIELDS if k in dataset_tensors}
         for k in ("rays", "rgbs"):
             if k not in self.fields:
@@ -213,16 +246,19 @@ class Trainer:
                                     lambda_ds=a.ds_lambda if getattr(a, "depth", False) else 0.0,
                                     GNLL=bool(getattr(a, "GNLL", False)), usealldepth=bool(getattr(a, "usealldepth", False)),
                                     lambda_ss=a.ss_lambda if getattr(a, "sem", False) else 0.0)
-        self.src = PhiloxRandom(seed=seed)
-        self.gather = BatchGather(self.fields, B)
+        # draws are keyed by the GLOBAL ray id: rank r's rays are rows r·b.. of the global batch
+        self.src = PhiloxRandom(seed=seed, ray_offset=rank * b)
+        self.gather = BatchGather(self.fields, b)
         # fixed device addresses of the step: the current row, the plan's state, the plan itself
         self.cur = torch.zeros(ROW_DTYPE.itemsize // 8, dtype=torch.int64, device=dev)
         self.noise_std_dev = self.cur.view(torch.float32)[0:1]          # &cur->noise_std
         self.state = torch.zeros(4, dtype=torch.int64, device=dev)      # spnerf_train_state
         self.plan_rows = torch.zeros(self.spe * (ROW_DTYPE.itemsize // 8), dtype=torch.int64, device=dev)
         self.perm = torch.zeros(self.spe * B, dtype=torch.int64, device=dev)
-        self.batch_idx = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.batch_idx = torch.zeros(b, dtype=torch.int64, device=dev)
         self.one = torch.ones((), device=dev)
+        if self.dp:
+            self._init_dp()
         self.global_step = 0          # steps done
         self._plan_epoch = None       # epoch of the uploaded plan
         self._host_plan = None
@@ -232,6 +268,87 @@ class Trainer:
         self._static_loss = None
         self._warm = set()            # loss forms that have run eagerly once
         self.counts = {"replay": 0, "eager": 0, "capture": 0, "plan_upload": 0}
+
+    # ------------------------------------------------------------------ data parallelism
+    def _join_group(self, world: int, rank: int, group, collectives: str) -> int:
+        """Check the process group against ``world`` and settle ``collectives``; this rank."""
+        import torch.distributed as dist
+        if group is None:
+            if not dist.is_initialized():
+                raise NotImplementedError(f"Trainer: world = {world} without a torch.distributed process group is not "
+                                          "implemented: start one process per GPU, call dp.init_from_env() and pass "
+                                          "world (and group)")
+            group = self.group = dist.group.WORLD
+        elif rank != 0:
+            raise ValueError("Trainer: an explicit rank goes without a group (the group knows this process's rank)")
+        if dist.get_world_size(group) != world:
+            raise ValueError(f"Trainer: world = {world} but the process group has {dist.get_world_size(group)} ranks")
+        backend = str(dist.get_backend(group))
+        if collectives == "graph" and backend != "nccl":
+            raise ValueError(f"Trainer: collectives='graph' needs the nccl backend (RCCL's all-reduce can be captured "
+                             f"into the step's graph), this group's is {backend!r}: use 'host'")
+        self.collectives = ("graph" if backend == "nccl" else "host") if collectives == "auto" else collectives
+        return dist.get_rank(group)
+
+    def _init_dp(self) -> None:
+        """The data-parallel step's fixed device buffers, its bindings and the gradient buckets."""
+        from . import _dp_lib
+        from .dp import GradBuckets
+        self._dl = _dp_lib
+        _dp_lib.lib()          # the same handle as self.lib with the dp signatures applied; no fallback
+        rays = self.fields["rays"]
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] < 8 or not rays.is_contiguous():
+            raise ValueError("Trainer: dataset_tensors['rays'] must be a contiguous (N, >= 8) fp32 tensor")
+        self.clamp = torch.zeros(2, dtype=torch.float32, device=self.dev)    # near / far of the global batch's first ray
+        self.labels_global = None
+        self._sems = None
+        if getattr(self.args, "sem", False):
+            sems = self.fields["sems"]
+            if sems.dtype != torch.int64 or sems.numel() != rays.shape[0] or not sems.is_contiguous():
+                raise ValueError("Trainer: dataset_tensors['sems'] must be a contiguous int64 tensor of N labels")
+            self._sems = sems
+            self.labels_global = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
+        self.buckets = [GradBuckets(m, self.world, self.group) for m in self.nets]
+        in_nets = {id(p) for m in self.nets for p in m.parameters()}
+        self.loose = [p for p in self.params if id(p) not in in_nets]        # e.g. the t embedding
+        # (float)(1 / world), rounded once: Adam multiplies the all-reduce's SUM by it as it loads it
+        self.grad_scale = float(np.float32(1.0 / self.world))
+        # the marks are one event set per device: with one net every bucket can go behind its own
+        # mark; with two, the buckets wait for the whole backward instead
+        self._overlap = len(self.nets) == 1
+        self._tail_after_replay = False   # collectives == "host": reduce + Adam follow each replay
+
+    def _reduce(self, overlap: bool) -> None:
+        """All-reduce (SUM) of every gradient: each net's flat gradient in buckets — behind their
+        backward marks when ``overlap``, else behind the whole compute stream — and the parameters
+        outside a flat buffer in one more small all-reduce.  The SUM stays: Adam scales it."""
+        from . import dp
+        flats = []
+        for m, bk in zip(self.nets, self.buckets):
+            flat = dp._shared_flat([p.grad for p in m.parameters()]) if all(p.grad is not None for p in m.parameters()) \
+                else None
+            if flat is None:
+                raise _lib.SpnerfError("Trainer: a data-parallel step needs every SPNeRF parameter's gradient in the "
+                                       "model's flat buffer (use_flat_grads, no frozen parameter)")
+            bk.launch(flat, overlap=overlap and self._overlap, force=True)
+            flats.append(flat)
+        for bk, flat in zip(self.buckets, flats):
+            bk.finish(flat, force=True, scale=False)
+        dp.allreduce_grads(self.loose, self.world, self.group, scale=False, force=True)
+
+    def global_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """The loss of the GLOBAL batch (the reference's ``train/loss``) from this rank's ``step()``
+        result: a copy all-reduced (SUM) and divided by ``world`` — the colour, solar and depth terms
+        are sums over rays divided by the batch size and the CE is already rescaled by the loss
+        kernel, so the ranks' losses average to it.  A collective: every rank calls it.  Not part of
+        the step; with one rank and no group, a copy."""
+        out = loss.detach().clone()
+        if self.dp:
+            import torch.distributed as dist
+            dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.group)
+            if self.world > 1:
+                out.div_(self.world)
+        return out
 
     # ------------------------------------------------------------------ the plan, once per epoch
     def check_error(self) -> None:
@@ -262,15 +379,78 @@ class Trainer:
                  for i in have]
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
         numel = (ctypes.c_int64 * n)(*[self.params[i].numel() for i in have])
+        if self.dp:   # the gradients hold the all-reduce's SUM: scaled by 1/world as they are loaded
+            _lib.check(self.lib.spnerf_adam_step_dev_scaled(n, arr([self.params[i] for i in have]), arr(grads),
+                                                            arr([self.exp_avg[i] for i in have]),
+                                                            arr([self.exp_avg_sq[i] for i in have]), numel,
+                                                            _lib.ptr(self.cur), self.betas[0], self.betas[1], self.eps,
+                                                            self.grad_scale, _lib.stream_of(self.cur)),
+                       "adam_step_dev_scaled")
+            return
         _lib.check(self.lib.spnerf_adam_step_dev(n, arr([self.params[i] for i in have]), arr(grads),
                                                  arr([self.exp_avg[i] for i in have]),
                                                  arr([self.exp_avg_sq[i] for i in have]), numel, _lib.ptr(self.cur),
                                                  self.betas[0], self.betas[1], self.eps, _lib.stream_of(self.cur)),
                    "adam_step_dev")
 
+    def _dp_device_step(self, form, tail: bool = True):
+        """The data-parallel step in stream order: spnerf_dp_step_begin (the row, this rank's slice,
+        the shared clamp, the global labels), gather, render, loss, backward — and with ``tail`` the
+        gradient all-reduces (buckets behind the backward's marks) and the scaled Adam.  Without it
+        (the graph of ``collectives="host"``) ``_host_tail`` follows each replay."""
+        from .rendering import render_rays
+        from .spnerf import device_noise_std
+        a = self.args
+        use_beta, add_depth, add_sem = form
+        rays_all = self.fields["rays"]
+        _lib.check(self.lib.spnerf_dp_step_begin(_lib.ptr(self.state), _lib.ptr(self.plan_rows), _lib.ptr(self.perm),
+                                                 _lib.ptr(self.cur), _lib.ptr(self.batch_idx), None, self.B, self.rank,
+                                                 self.world, _lib.ptr(rays_all), rays_all.stride(0), _lib.ptr(self.clamp),
+                                                 _lib.ptr(self._sems), _lib.ptr(self.labels_global),
+                                                 _lib.stream_of(self.cur)), "dp_step_begin")
+        for p in self.params:
+            p.grad = None
+        bt = self.gather(self.batch_idx)
+        rays, rgbs = bt["rays"], bt["rgbs"]
+        depths, valid, dstd = bt.get("depths"), bt.get("valid_depth"), bt.get("depth_std")
+        sems = bt["sems"].reshape(-1) if getattr(a, "sem", False) else None
+        ts = bt["ts"].reshape(-1) if getattr(a, "beta", False) else None
+        lkw = {"labels_global": self.labels_global, "world": self.world} if sems is not None else {}
+        # The buckets go behind their backward marks where that pays: inside the capture of
+        # collectives="graph" (there the marks are the graph's edges) and in every step of
+        # graph=False.  The few eager steps of graph=True reduce behind the whole backward instead, so
+        # that a mark event is only ever recorded and waited for inside captures, or only outside.
+        overlap = tail and self._overlap and (torch.cuda.is_current_stream_capturing() or not self.graph_mode)
+        if overlap:
+            _lib.grad_marks_arm(True)     # the backward records the buckets' marks
+        try:
+            with random_source(self.src), device_noise_std(self.noise_std_dev):
+                res = render_rays(self.models, a, rays, ts, semantics=sems, mode="train", valid_depth=valid,
+                                  target_depths=depths, target_std=dstd, clamp_near_far=self.clamp)
+                loss, _ = self.floss(res, rgbs, depths, valid, dstd, sems, use_beta=use_beta, add_depth=add_depth,
+                                     add_sem=add_sem, **lkw)
+                loss.backward(self.one)
+            if tail:
+                self._reduce(overlap=overlap)
+        finally:
+            if overlap:
+                _lib.grad_marks_arm(False)
+        if tail:
+            self._adam()
+        return loss.detach()
+
+    def _host_tail(self) -> None:
+        """What follows a replay of the ``collectives="host"`` graph on the stream: the buckets behind
+        the whole replay, the loose parameters' all-reduce, Adam — a few host calls, no host sync of
+        the trainer's own."""
+        self._reduce(overlap=False)
+        self._adam()
+
     def _device_step(self, form):
         """Everything a step does on the device, in stream order — the body of the captured graph:
         schedule + batch (step_begin), gather, render, loss, backward, Adam."""
+        if self.dp:
+            return self._dp_device_step(form)
         from .rendering import render_rays
         from .spnerf import device_noise_std
         a = self.args
@@ -299,8 +479,14 @@ class Trainer:
         for p in self.params:
             p.grad = None
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._static_loss = self._device_step(form)
+        if self.dp and self.collectives == "host":
+            # the graph ends with the backward; the collectives and Adam follow each replay
+            with torch.cuda.graph(g):
+                self._static_loss = self._dp_device_step(form, tail=False)
+            self._tail_after_replay = True
+        else:   # with collectives="graph" the bucket all-reduces are captured behind their marks
+            with torch.cuda.graph(g):
+                self._static_loss = self._device_step(form)
         # the packed-weight buffers the capture wrote into live exactly as long as the graph
         self._graph_keep = [m.release_graph_packs() for m in self.nets]
         self._graph, self._graph_form = g, form
@@ -319,6 +505,8 @@ class Trainer:
         if self._graph is not None and self._plan_epoch == (t - 1) // self.spe and \
                 self._graph_form == loss_form(t, self.args, self.spe):
             self._graph.replay()
+            if self.dp and self._tail_after_replay:
+                self._host_tail()
             self.counts["replay"] += 1
             self.global_step = t
             return self._static_loss
@@ -340,6 +528,8 @@ class Trainer:
             if self._graph is None:
                 self._capture(form)
             self._graph.replay()
+            if self.dp and self._tail_after_replay:
+                self._host_tail()
             self.counts["replay"] += 1
             loss = self._static_loss
         self.global_step = t
@@ -364,11 +554,14 @@ class Trainer:
         return {"models": {k: {n: v.detach().clone() for n, v in m.state_dict().items()} for k, m in self.models.items()},
                 "exp_avg": [t.clone() for t in self.exp_avg], "exp_avg_sq": [t.clone() for t in self.exp_avg_sq],
                 "global_step": self.global_step, "philox_step": self.src.sync_host_step(),
-                "plan_cursor": self.global_step % self.spe, "seed": self.schedule.seed}
+                "plan_cursor": self.global_step % self.spe, "seed": self.schedule.seed, "world": self.world}
 
     def load_state_dict(self, sd: dict) -> None:
         if sd["seed"] != self.schedule.seed:
             raise ValueError(f"Trainer.load_state_dict: saved with seed {sd['seed']}, this trainer has {self.schedule.seed}")
+        if sd.get("world", 1) != self.world:   # the Philox ray offsets and the ranks' slices would differ
+            raise ValueError(f"Trainer.load_state_dict: saved with world = {sd.get('world', 1)}, this trainer has "
+                             f"{self.world}")
         if sd["plan_cursor"] != sd["global_step"] % self.spe:
             raise ValueError("Trainer.load_state_dict: the plan cursor does not match this dataset and batch size")
         self._drop_graph()

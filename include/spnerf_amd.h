@@ -187,19 +187,27 @@ int32_t spnerf_sample_stratified(int64_t n_rays, int32_t n_samples, const float*
 /* GenerateGuidedSamples + sort + merge (rendering.py:92-116,165-167): 3-sigma window around
  * the pass-1 depth, replaced by the GT window on rays with valid_depth > 0 (valid_depth may be
  * NULL = test mode), clamped to clamp_nf[0..1] (device; the chunk's first-ray near/far,
- * rendering.py:95,113).  u_pred / u_gt are (n_rays, n).  Writes z_sorted = sort([z, z2]) and
- * z_unsort = [z, sort(z2)], both (n_rays, 2n). */
+ * rendering.py:95,113).  u_pred / u_gt are (n_rays, n), one row per ray.  Writes z_sorted =
+ * sort([z, z2]) and z_unsort = [z, sort(z2)], both (n_rays, 2n).  2 <= n_samples <= 128.
+ * A window of zero width (all of pass 1's weight on one sample, an empty ray, target_std = 0)
+ * gives n copies of the window centre clamped to clamp_nf, always finite; the reference divides
+ * 0 by 0 there and returns NaN, which inside a captured training graph would poison every later
+ * step. */
 int32_t spnerf_sample_guided(int64_t n_rays, int32_t n_samples, const float* z, const float* depth,
                              const float* weights, const float* clamp_nf, const int64_t* valid_depth,
                              const float* target_depths, int32_t td_stride, const float* target_std,
                              const float* u_pred, const float* u_gt, float* z_sorted, float* z_unsort,
                              const spnerf_rng* rng, void* stream);
 /* sample_pdf (rendering.py:14-55): bins (n_rays, n_bins+1), weights (n_rays, n_bins),
- * u (n_rays, n_imp) → samples (n_rays, n_imp). n_bins+1 <= 256, n_imp <= 256. */
+ * u (n_rays, n_imp) → samples (n_rays, n_imp). 1 <= n_bins, n_bins+1 <= 256; n_imp >= 1, any
+ * count. */
 int32_t spnerf_sample_pdf(int64_t n_rays, int32_t n_bins, const float* bins, const float* weights,
                           int32_t n_imp, const float* u, float eps, float* samples, const spnerf_rng* rng,
                           void* stream);
-/* sample_3sigma (rendering.py:58-73): low/high (n_rays), u (n_rays, n) → (n_rays, n) */
+/* sample_3sigma (rendering.py:58-73): low/high (n_rays), u (n_rays, n) → (n_rays, n),
+ * 2 <= n <= 256.  A window whose float step (high - low) / (n - 1) is 0 (low == high, or a
+ * spread that underflows) gives n copies of low clamped to clamp_nf (finite; NaN in the
+ * reference, see spnerf_sample_guided). */
 int32_t spnerf_sample_3sigma(int64_t n_rays, int32_t n, const float* low, const float* high,
                              const float* clamp_nf, const float* u, float* out, void* stream);
 /* row-wise ascending sort of (n_rays, n) floats, n <= 256 (torch.sort(-1) values) */

@@ -87,16 +87,21 @@ __device__ __forceinline__ float invert_cdf(const WaveLds& L, int nb, float u, f
     return b0 + (u - c0) / den * (b1 - b0);
 }
 
-// sample_3sigma bin edges / Gaussian bin weights of one ray into L.bins and w (N edges, N-1 bins)
+// sample_3sigma bin edges / Gaussian bin weights of one ray into L.bins and w (N edges, N-1 bins).
+// A window of zero width (step == 0: all of pass 1's weight on one sample, an empty ray, a GT
+// spread of 0, or a spread so small that the step underflows) has factor = x / 0 in the reference,
+// which returns NaN there; here every edge is the clamped centre and every weight 0, so the N
+// samples are that centre (spnerf_amd.h).
 template <int EPL>
 __device__ void window_bins(WaveLds& L, float (&w)[EPL], float low, float high, int N, float nr, float fr, int lane) {
     const float step = (high - low) / (float)(N - 1);
+    const bool flat = step == 0.f;  // high == low, or a spread so small that the step underflows
     float edge[EPL];
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
         const int e = lane * EPL + j;
         const float t = linspace_at(0.f, 1.f, N, e < N ? e : 0);
-        float v = __fadd_rn(__fmul_rn(low, __fsub_rn(1.f, t)), __fmul_rn(high, t));
+        float v = flat ? low : __fadd_rn(__fmul_rn(low, __fsub_rn(1.f, t)), __fmul_rn(high, t));
         v = fminf(fmaxf(v, nr), fr);  // Tensor.clamp(near, far)
         edge[j] = v;
         if (e < N) L.bins[e] = v;
@@ -109,7 +114,7 @@ __device__ void window_bins(WaveLds& L, float (&w)[EPL], float low, float high, 
         w[j] = 0.f;
         if (e < N - 1) {
             const float en = j + 1 < EPL ? edge[j + 1] : en0;
-            const float factor = (en - edge[j]) / step;
+            const float factor = flat ? 0.f : (en - edge[j]) / step;
             const float x = linspace_at(-3.f, 3.f, N - 1, e);
             w[j] = factor * (gc * expf(-0.5f * (x * x)));
         }

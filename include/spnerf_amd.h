@@ -66,6 +66,10 @@ typedef struct spnerf_rng {
 #define SPNERF_MLP_ACCUMULATE 8  /* backward: add into grad_flat instead of overwriting it   */
 #define SPNERF_MLP_DEFER_TRUNK_WGRAD 16  /* backward: leave the trunk (and sun_v 2/4) weight gradients to
                                           * spnerf_mlp_trunk_wgrad (the workspace must stay intact) */
+#define SPNERF_MLP_KEEP_FEAT 32  /* forward of every head, nothing saved: run the heads in launches of their
+                                  * own so that G (xyz_features, the first `width` columns of its rows) stays
+                                  * in the workspace for the relight launches of spnerf_amd_relight.h;
+                                  * without the flag every launch is what it was */
 
 /* composite flags */
 #define SPNERF_COMP_WEIGHTS_ONLY 1  /* weights, transparency, depth only (no rgb / sem)      */

@@ -20,6 +20,8 @@ from .spnerf import (SPNeRF, Mapping, Siren, first_layer_sine_init, inference, i
                      sine_init)
 from . import view  # noqa: F401  (whole views: image products and the validation scores on the GPU)
 from .view import render_image, view_loss, view_metrics  # noqa: F401
+from . import relight  # noqa: F401  (a view under K sun directions from one pass over its geometry)
+from .relight import relight_image  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

@@ -14,11 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # SPNERF_AMD_LIB: another in-tree build of the same sources (A/B runs of compile-time variants)
 LIB_PATH = os.path.join(HERE, os.environ.get("SPNERF_AMD_LIB", "libspnerf_amd.so"))
 
+SPNERF_OK, SPNERF_E_ARG, SPNERF_E_HIP, SPNERF_E_UNSUPPORTED = 0, -1, -2, -3
 SPNERF_MLP_SAVE = 1
 SPNERF_MLP_SIGMA_ONLY = 2
 SPNERF_MLP_SUN_ONLY = 4
 SPNERF_MLP_ACCUMULATE = 8
 SPNERF_MLP_DEFER_TRUNK_WGRAD = 16
+SPNERF_MLP_KEEP_FEAT = 32
 SPNERF_COMP_WEIGHTS_ONLY = 1
 SPNERF_COMP_SUN_COLUMN = 2
 

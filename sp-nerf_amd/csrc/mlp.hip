@@ -1214,6 +1214,7 @@ struct Ctx {
     int S;
     int acc = 0;     // backward: gradient reductions add into the flat gradient
     int defer = 0;   // backward: the trunk layers' weight gradients are left to spnerf_mlp_trunk_wgrad
+    int keep_feat = 0;  // forward (SPNERF_MLP_KEEP_FEAT): the heads in launches of their own, G left in the workspace
     // the forward's ray inputs (the fused inference trunk encodes layer 0's input itself)
     const float* rays = nullptr;
     const float* z = nullptr;
@@ -1484,7 +1485,7 @@ static bool fused_trunk_on(const Ctx& c) {
 }
 // inference (nothing saved) of the full or the σ-only heads: the fused heads kernel after the trunk
 static bool heads_fused_on(const Ctx& c, bool save, int mode) {
-    return !save && (mode == 0 || mode == 1) && c.d.bf && c.k.Ffeat16 >= 0 && heads_bf16_supported(c.d);
+    return !c.keep_feat && !save && (mode == 0 || mode == 1) && c.d.bf && c.k.Ffeat16 >= 0 && heads_bf16_supported(c.d);
 }
 int g_pe_inline = 1;  // option "pe_inline": inference trunk with layer 0 encodes o + dir·z itself (no k_encode)
 static bool trunk_l0_on(const Ctx& c, bool save);
@@ -1797,6 +1798,9 @@ static int32_t mlp_forward(const Dims& d, const float* packed, const float* rays
     const int W = d.W, H = d.H;
     if (P == 0) return SPNERF_OK;
     SPN_ARG(P < (1ll << 31) / std::max(d.NQ, d.NG), "too many points (%lld) for one call", (long long)P);
+    SPN_ARG(!(flags & SPNERF_MLP_KEEP_FEAT) || (!save && mode == 0 && n_total < 0),
+            "SPNERF_MLP_KEEP_FEAT goes with a whole non-saving forward of every head");
+    c.keep_feat = (flags & SPNERF_MLP_KEEP_FEAT) ? 1 : 0;
     SPN_ARG(!d.sem || labels, "semantic model needs labels");
     SPN_ARG(!d.beta || mode != 0 || temb, "beta model needs t_emb");
 

@@ -211,12 +211,15 @@ def render_rays(models, args, rays, ts, semantics=None, mode='test', valid_depth
     return out
 
 
-def _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth, target_depths, target_std, clamp_near_far):
+def _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth, target_depths, target_std, clamp_near_far,
+                 rows_mlp=None):
     """The coarse main pass of a render up to its MLP rows, shared by ``render_rays`` and
     ``view.render_image``: the stratified depths, the guided passes when ``args.guidedsample``, and
     the main pass's rows at the final depths — everything before the compositing.  ``rays`` is a
     non-empty contiguous fp32 device tensor.  Returns (model, weight pack, semantics or None,
-    t-embedding or None, out (B·S, number_of_outputs), z_vals (B, S), z_vals_unsort or None)."""
+    t-embedding or None, out (B·S, number_of_outputs), z_vals (B, S), z_vals_unsort or None).
+    ``rows_mlp`` (renders without gradients): what runs the forwards of the returned rows in
+    ``run_mlp``'s place (relight.py)."""
     N_samples = args.n_samples
     B = rays.shape[0]
     begin_render(rays.device)         # a keyed on-device random source starts a new step
@@ -243,8 +246,11 @@ def _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth, target_de
                            target_std, cnf)
 
         t_in = rays_t if model.beta else None
-        run = guided_main_pass if mlp_saves(model, t_in) else guided_inference_pass
-        out, z_vals, z_unsort = run(model, rays, z_vals, sem if model.sem else None, t_in, guide, pk)
+        if mlp_saves(model, t_in):
+            out, z_vals, z_unsort = guided_main_pass(model, rays, z_vals, sem if model.sem else None, t_in, guide, pk)
+        else:
+            out, z_vals, z_unsort = guided_inference_pass(model, rays, z_vals, sem if model.sem else None, t_in, guide, pk,
+                                                          rows_mlp)
         return model, pk, sem, rays_t, out, z_vals, z_unsort
     z_unsort = None
     if args.guidedsample:
@@ -252,7 +258,7 @@ def _coarse_rows(models, args, rays, ts, semantics, mode, valid_depth, target_de
             res1 = inference_rays(model, args, rays, z_vals, 3, sem, rays_t, mode="sigma", pack=pk)
         cnf = None if clamp_near_far is None else clamp_near_far.reshape(2).to(rays.device, torch.float32).contiguous()
         z_vals, z_unsort = _guided(res1, z_vals, N_samples, rays, mode, valid_depth, target_depths, target_std, cnf)
-    out = run_mlp(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
+    out = (rows_mlp or run_mlp)(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
     return model, pk, sem, rays_t, out, z_vals, z_unsort
 
 
@@ -266,7 +272,7 @@ def sort_rows(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _fine_rows(models, args, rays, ts, z_vals, weights_coarse, semantics):
+def _fine_rows(models, args, rays, ts, z_vals, weights_coarse, semantics, rows_mlp=None):
     """The fine pass up to its MLP rows (rendering.py:186-203), shared by ``_fine`` and
     ``view.render_image``: the importance depths drawn from the coarse weights, merged and sorted,
     and the fine model's rows there.  Returns (model, weight pack, semantics or None, t-embedding
@@ -282,7 +288,7 @@ def _fine_rows(models, args, rays, ts, z_vals, weights_coarse, semantics):
         rays_t = models['t'](ts) if ts else None                                    # :201, as written there
     sem = semantics if model.sem else None
     pk = pack_for_render(model)
-    out = run_mlp(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
+    out = (rows_mlp or run_mlp)(model, rays, z_vals, 3, sem if model.sem else None, rays_t if model.beta else None, pack=pk)
     return model, pk, sem, rays_t, out, z_vals
 
 

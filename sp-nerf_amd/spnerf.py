@@ -521,19 +521,24 @@ def mlp_saves(model: SPNeRF, temb=None) -> bool:
                                         (temb is not None and temb.requires_grad))
 
 
-def guided_inference_pass(model: SPNeRF, rays, z1, labels, temb, guide, pack: "WeightPack"):
+def guided_inference_pass(model: SPNeRF, rays, z1, labels, temb, guide, pack: "WeightPack", mlp=None):
     """The no-gradient twin of ``guided_main_pass``: pass 1 runs every head over the stratified
     depths (instead of σ alone), the second forward only the guided ones, and
-    ``spnerf_merge_samples`` gathers both into the sorted order — each point evaluated once."""
+    ``spnerf_merge_samples`` gathers both into the sorted order — each point evaluated once.
+    ``mlp``: what runs the two forwards in ``run_mlp``'s place (relight.py keeps per-point values
+    of each and is told the order they were merged in through its ``merged``)."""
     B, S = z1.shape
+    run = run_mlp if mlp is None else mlp
     with torch.no_grad():
-        out1 = run_mlp(model, rays, z1, 3, labels, temb, pack=pack)
+        out1 = run(model, rays, z1, 3, labels, temb, pack=pack)
         z_sorted, z_unsort = guide(out1, z1)
-        out2 = run_mlp(model, rays, z_unsort[:, S:].contiguous(), 3, labels, temb, pack=pack)
+        out2 = run(model, rays, z_unsort[:, S:].contiguous(), 3, labels, temb, pack=pack)
         out = torch.empty(B * 2 * S, model.number_of_outputs, dtype=torch.float32, device=rays.device)
         _lib.check(_lib.lib().spnerf_merge_samples(B, S, S, _lib.ptr(z_unsort), _lib.ptr(out1), _lib.ptr(out2),
                                                    model.number_of_outputs, _lib.ptr(out), _lib.stream_of(out1)),
                    "merge_samples")
+        if mlp is not None:
+            mlp.merged(B, S, z_unsort)
     return out, z_sorted, z_unsort
 
 

@@ -14,6 +14,7 @@ march of every chunk is reduced to two numbers per ray (csrc/val.hip, include/sp
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -36,16 +37,25 @@ _PLANES = {"rgb": (lambda c: (3,), torch.float32), "depth": (lambda c: (), torch
 _COMPOSITE_PLANES = ("rgb", "depth", "sun", "albedo", "sky", "beta", "sem_logits", "sem_class")
 
 
-def composite_products(model, out, z, noise_std, planes: dict, ray_begin: int = 0) -> None:
-    """``spnerf_view_composite_products`` on one chunk's final-pass rows: ray r of the chunk goes
-    to entry ``ray_begin + r`` of every plane in ``planes`` (name -> contiguous device tensor; the
-    names of ``spnerf_view_planes``, a missing name is a skipped plane).  Takes the σ-noise draw the
-    composite of that pass takes (spnerf.py:122)."""
+def sigma_noise_draw(z, noise_std):
+    """The σ-noise draw the composite of a pass takes (spnerf.py:122): (key, keep-alive, noise) —
+    an on-device key, or a host-side draw (None when ``noise_std`` is 0)."""
     B, S = z.shape
     key, keep = device_key(z.device)   # on-device σ noise: a slot per inference call, drawn or not
     noise = None if key is not None else current_random_source().noise((B, S), z.device, noise_std)
     if noise is not None:
         noise = noise.contiguous().float()
+    return key, keep, noise
+
+
+def composite_products(model, out, z, noise_std, planes: dict, ray_begin: int = 0, draw=None) -> None:
+    """``spnerf_view_composite_products`` on one chunk's final-pass rows: ray r of the chunk goes
+    to entry ``ray_begin + r`` of every plane in ``planes`` (name -> contiguous device tensor; the
+    names of ``spnerf_view_planes``, a missing name is a skipped plane).  Takes the σ-noise draw the
+    composite of that pass takes (spnerf.py:122), or ``draw`` (``sigma_noise_draw``'s result: a
+    draw shared with another launch over the same rows)."""
+    B, S = z.shape
+    key, keep, noise = sigma_noise_draw(z, noise_std) if draw is None else draw
     z = z.contiguous()
     n_sem = model.num_sem_classes if model.sem else 0
     p = _view_lib.ViewPlanes()
@@ -63,14 +73,51 @@ def composite_products(model, out, z, noise_std, planes: dict, ray_begin: int = 
         _lib.stream_of(out)), "view_composite_products")
 
 
-def _final_rows(models, args, rays, ts, semantics, clamp_near_far=None, rgb_coarse=None, solar=False):
+def _chunk_plan(model, args, rays, chunk, clamp_near_far):
+    """(rays per chunk, guided-sampling clamp) of a whole-view loop: the defaults of ``render_image``."""
+    S = (2 if args.guidedsample else 1) * args.n_samples + args.n_importance
+    if chunk is None:
+        chunk = max(1, max_points_per_call(model) // S)
+    if clamp_near_far is None and args.guidedsample and rays.shape[0]:
+        clamp_near_far = rays[0, 6:8]
+    return int(chunk), clamp_near_far
+
+
+def _check_coarse_plane(coarse, n_rays):
+    if coarse is not None and (not coarse.is_cuda or coarse.dtype != torch.float32 or not coarse.is_contiguous() or
+                               tuple(coarse.shape[1:]) != (3,) or coarse.shape[0] < n_rays):
+        raise ValueError(f"plane 'rgb_coarse': expected a contiguous float32 device tensor of at least {n_rays} x 3, got "
+                         f"{coarse.dtype} {tuple(coarse.shape)} on {coarse.device}")
+
+
+def _ray_chunks(N, chunk, ray_offset):
+    """The (i0, i1) of a whole-view loop over N rays.  With an on-device random source every chunk
+    draws as step 0 of the global ray ids ``ray_offset + i``; the source's own offset is put back
+    when the generator is closed (use it under ``contextlib.closing``)."""
+    src = current_random_source()
+    keyed = getattr(src, "on_device", False)
+    offset0 = src.ray_offset if keyed else 0
+    try:
+        for i0 in range(0, N, int(chunk)):
+            if keyed:
+                src.ray_offset = int(ray_offset) + i0
+                src.reset_step(-1)
+            yield i0, min(N, i0 + int(chunk))
+    finally:
+        if keyed:
+            src.ray_offset = offset0
+
+
+def _final_rows(models, args, rays, ts, semantics, clamp_near_far=None, rgb_coarse=None, solar=False, rows_mlp=None):
     """(model, out, z_vals) of the pass whose composite is the image: render_rays(mode='test')
     up to that composite, the solar march (``sc_lambda``) left to the caller.  ``rgb_coarse`` (with
     a fine model): a (B, 3) slice of the coarse image's plane, filled here.  With ``solar`` a
     fourth value follows: (weight pack, semantics or None, t-embedding or None) of the model, what
-    the solar pass at the same depths needs."""
+    the solar pass at the same depths needs.  ``rows_mlp``: what runs the forwards of the
+    returned rows in ``run_mlp``'s place (relight.py)."""
     model, pk, sem, rays_t, out, z_vals, _ = _coarse_rows(models, args, rays, ts, semantics, "test", None, None, None,
-                                                                 clamp_near_far)
+                                                                 clamp_near_far,
+                                                                 None if args.n_importance > 0 else rows_mlp)
     if args.n_importance > 0:
         if rgb_coarse is None:
             # the coarse weights alone: the σ-only composite takes the same noise draw and marches alike
@@ -78,7 +125,7 @@ def _final_rows(models, args, rays, ts, semantics, clamp_near_far=None, rgb_coar
         else:   # the coarse image as well: the full composite, the same draw, the same march and weights
             rgb, _, w, _, _ = composite(model, out, z_vals, args.noise_std)
             rgb_coarse.copy_(rgb)
-        model, pk, sem, rays_t, out, z_vals = _fine_rows(models, args, rays, ts, z_vals, w, semantics)
+        model, pk, sem, rays_t, out, z_vals = _fine_rows(models, args, rays, ts, z_vals, w, semantics, rows_mlp)
     if solar:
         return model, out, z_vals, (pk, sem, rays_t)
     return model, out, z_vals
@@ -178,27 +225,13 @@ def render_image(models, args, rays, ts=None, semantics=None, *, chunk=None,
         planes = {n: out[n] for n in names}
     else:
         planes = {n: torch.empty((N,) + _PLANES[n][0](n_sem), dtype=_PLANES[n][1], device=dev) for n in names}
-    S = (2 if args.guidedsample else 1) * args.n_samples + args.n_importance
-    if chunk is None:
-        chunk = max(1, max_points_per_call(model) // S)
-    if clamp_near_far is None and args.guidedsample and N:
-        clamp_near_far = rays[0, 6:8]
+    chunk, clamp_near_far = _chunk_plan(model, args, rays, chunk, clamp_near_far)
     composited = {n: t for n, t in planes.items() if n in _COMPOSITE_PLANES}
     coarse = planes.get("rgb_coarse")
-    if coarse is not None and (not coarse.is_cuda or coarse.dtype != torch.float32 or not coarse.is_contiguous() or
-                               tuple(coarse.shape[1:]) != (3,) or coarse.shape[0] < begin + N):
-        raise ValueError(f"plane 'rgb_coarse': expected a contiguous float32 device tensor of at least {begin + N} x 3, got "
-                         f"{coarse.dtype} {tuple(coarse.shape)} on {coarse.device}")
-    src = current_random_source()
-    keyed = getattr(src, "on_device", False)
-    offset0 = src.ray_offset if keyed else 0
-    try:
+    _check_coarse_plane(coarse, begin + N)
+    with contextlib.closing(_ray_chunks(N, chunk, ray_offset)) as chunks:
         with torch.no_grad():
-            for i0 in range(0, N, int(chunk)):
-                i1 = min(N, i0 + int(chunk))
-                if keyed:
-                    src.ray_offset = int(ray_offset) + i0
-                    src.reset_step(-1)
+            for i0, i1 in chunks:
                 ts_c = None if ts is None else ts[i0:i1]
                 sem_c = None if semantics is None else semantics[i0:i1]
                 m, rows, z, *extra = _final_rows(models, args, rays[i0:i1], ts_c, sem_c, clamp_near_far,
@@ -208,9 +241,6 @@ def render_image(models, args, rays, ts=None, semantics=None, *, chunk=None,
                     pk, sem, rays_t = extra[0]
                     solar_terms(m, rays[i0:i1], z, args.noise_std, pk, sem, rays_t, planes["sc_term2"], planes["sc_term3"],
                                 begin + i0)
-    finally:
-        if keyed:
-            src.ray_offset = offset0
     res = dict(planes)
     if center is not None:
         from .dsm import _points

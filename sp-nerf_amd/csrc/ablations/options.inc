@@ -1,4 +1,4 @@
-    // The ablation build's entries of option_slot (mlp.hip, included there under SPN_ABLATIONS).
+    // The ablation build's entries of option_slot (options.cpp, included there under SPN_ABLATIONS).
     // A/B switches of kernels measured slower than the defaults (DESIGN.md §6, Appendix B) and
     // profiling ablations whose outputs are INVALID: only in a -DSPN_ABLATIONS build
     // (make -C sp-nerf_amd variant VDEF=-DSPN_ABLATIONS VLIB=libspnerf_amd_abl.so)

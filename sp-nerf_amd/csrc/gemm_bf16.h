@@ -96,7 +96,7 @@ int tn_splits_bf16(int P, int N, int K, int variant = -1, int few = -1, int cus 
 int32_t gemm_tn_bf16(const TN16Args& a, int splits, hipStream_t s);
 
 // Up to kTnGroup weight-gradient GEMMs (each its own operands, shape and slabs) in ONE launch
-// of the DMA kernel, splits[i] point splits for GEMM i (option tn_group in mlp.hip): a 512 x 512
+// of the DMA kernel, splits[i] point splits for GEMM i (option tn_group in mlp_backward.hip): a 512 x 512
 // GEMM has 4 tiles, so alone it fills the CUs with 64 splits and writes 64 MB of partial slabs;
 // n of them together need 1/n of the splits each (n x fewer slab bytes, one launch, one tail).
 constexpr int kTnGroup = 10;

@@ -252,7 +252,7 @@ WS ws_layout(const Dims& d, int64_t n_rays, int32_t S, int32_t flags) {
         need(d.NQ, W);
         need(H, H);
         if (d.bf && d.W % 256 == 0) {
-            // grouped weight gradients (mlp.hip trunk_wgrad, option tn_group): up to
+            // grouped weight gradients (mlp_backward.hip trunk_wgrad, option tn_group): up to
             // kTnGroupRounds x kLayoutCus 256 x 256 blocks of the DMA kernel, each its own slab tile,
             // over both passes' points (at most 2P here; trunk_wgrad clamps to this capacity)
             const int64_t blocks = std::min<int64_t>((int64_t)kTnGroupRounds * kLayoutCus,
@@ -275,10 +275,10 @@ WS ws_layout(const Dims& d, int64_t n_rays, int32_t S, int32_t flags) {
         w.gemb = take(B * (d.sd ? d.sd : 1));
         w.embr = take(B * (d.sd ? d.sd : 1));
         // skinny slabs: one point reduction at a time, or the per-ray batch (≤ kSkinnyMulti tasks of
-        // ≤ 9 rows x max(W, H) columns each, mlp.hip SkinnyBatch)
+        // ≤ 9 rows x max(W, H) columns each, mlp_ctx.h SkinnyBatch)
         // chunks of any row count up to P (resp. B): skinny_chunk's bound
         const int64_t cP = std::min<int64_t>((P + 63) / 64, 768), cB = std::min<int64_t>((B + 63) / 64, 768);
-        // the point batch of a backward (mlp.hip step 2): σ (1 x W), sun (1 x H), albedo (3 x H), β
+        // the point batch of a backward (mlp_backward.hip step 2): σ (1 x W), sun (1 x H), albedo (3 x H), β
         // (1 x H) and the C semantic logits (C x H) — 5 + C rows, more than 9 from five classes on
         // (at point counts small enough for one chunk per 64 points, the backward of a 5-class model
         // stopped at "skinny batch: slab capacity")

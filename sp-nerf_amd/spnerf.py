@@ -4,7 +4,7 @@
 shapes (so reference checkpoints load with ``load_state_dict``, and ``torch.manual_seed(s)``
 gives the same initial weights: the RNG-consuming constructors run in the reference's order,
 spnerf.py:162-264), but its forward pass is the HIP library: positional encoding, the
-8-layer SIREN trunk and every head run as gfx950 kernels (csrc/mlp.hip, csrc/gemm_f32.hip),
+8-layer SIREN trunk and every head run as gfx950 kernels (csrc/mlp_forward.hip, csrc/gemm_f32.hip),
 with a hand-written backward (``spnerf_mlp_backward``) behind ``torch.autograd.Function``.
 
 ``inference`` (spnerf.py:63-159) composites with the wavefront-scan kernels of
@@ -593,7 +593,7 @@ def run_mlp(model: SPNeRF, rays: torch.Tensor, z: torch.Tensor, dir_offset: int,
 
 
 def max_points_per_call(model: SPNeRF) -> int:
-    """Largest B·S one spnerf_mlp_forward accepts (mlp.hip: P < 2^31 / max(NQ, NG))."""
+    """Largest B·S one spnerf_mlp_forward accepts (mlp_forward.hip: P < 2^31 / max(NQ, NG))."""
     H = model.feat // 2
     nq = 2 * H + (H if model.beta else 0)
     ng = model.feat + (H if model.sem else 0)

@@ -303,14 +303,26 @@ def render_ortho(models, args, grid, min_alt, max_alt, center, rng, sun, *, ts=0
 
 
 def relight_ortho(models, args, grid, min_alt, max_alt, center, rng, sun_dirs, *, ts=0, semantics=None, supersample=1,
-                  products=("rgb", "sun", "sky"), chunk=None, rows=None) -> dict:
+                  products=("rgb", "sun", "sky"), chunk=None, rows=None, cast=False) -> dict:
     """``render_ortho`` over ``relight_image``: the cells of ``grid`` under the K sun directions
     ``sun_dirs`` (K, 3) from one pass over their geometry.  The sun-dependent planes come back as
     "rgb" (K, rows, xsize, 3), "sun" (K, rows, xsize) and "sky" (K, rows, xsize, 3); the others once,
-    as ``render_ortho`` shapes them.  With "depth" among the products "dsm" comes back too."""
+    as ``render_ortho`` shapes them.  With "depth" among the products "dsm" comes back too.
+
+    ``cast=True`` adds "shadow_geo" (K, ysize, xsize) uint8: the geometric shadows of that "dsm" under
+    ``sun_dirs`` (``shadow.cast_shadows``), to hold the learnt "sun" against
+    (``shadow.shadow_agreement``).  It needs "depth" among the products and the whole grid
+    (``rows=None``): a band lacks the occluders outside it.  The other planes do not change."""
     s, j0, j1, scene = _plan(models, args, grid, min_alt, max_alt, center, rng, ts, semantics, supersample, products, rows,
                              RELIGHT_PRODUCTS, "relight_ortho")
     dirs = _directions(sun_dirs)
+    if cast:
+        from . import shadow
+        if "depth" not in products:
+            raise ValueError('cast=True casts the shadows of the call\'s own DSM: it needs "depth" among the products')
+        if rows is not None:
+            raise ValueError("cast=True needs the whole grid (rows=None): a band lacks the occluders outside it")
+        shadow.sun_directions(dirs)
     if "rgb_coarse" in products and not args.n_importance > 0:
         raise ValueError("the rgb_coarse product is the coarse image beside a fine model's: it needs n_importance > 0")
     rays, ts_rays, sem_rays, offset, clamp = _grid_inputs(models, args, grid, s, j0, j1, scene, dirs[0].numpy(), ts, semantics)
@@ -322,4 +334,6 @@ def relight_ortho(models, args, grid, min_alt, max_alt, center, rng, sun_dirs, *
     out = _to_grid(img, s, j1 - j0, grid.xsize, SUN_PLANES)
     if "alt" in out:
         out["dsm"] = out["alt"]
+    if cast:
+        out["shadow_geo"] = shadow.cast_shadows(out["dsm"], grid, dirs)
     return out

@@ -26,6 +26,8 @@ from . import ortho  # noqa: F401  (a DSM and true-ortho products on a UTM groun
 from .ortho import GroundGrid, ortho_rays, relight_ortho, render_ortho  # noqa: F401
 from . import shadow  # noqa: F401  (geometric shadows of a ground-grid DSM under K sun directions)
 from .shadow import cast_shadows, shadow_agreement  # noqa: F401
+from . import rectify  # noqa: F401  (camera images on the ground grid over a DSM: projection, sampling, occlusion, mosaic)
+from .rectify import orthorectify  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

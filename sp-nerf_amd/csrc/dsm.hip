@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "utm.h"
 
 namespace spn {
 
@@ -30,36 +31,6 @@ struct DsmPointArgs {
     double* lla;  // [n][3] lat, lon (degrees), alt, or null
     double* ena;  // [n][3] easting, northing, alt, or null
 };
-
-// WGS-84 transverse Mercator (UTM) by Krüger's series to 6th order in n (utm_krueger in
-// oracle/dsm_ref.py is the same arithmetic in numpy)
-__device__ __forceinline__ void utm_forward(double lat_deg, double lon_deg, int zone, int south, double* e, double* nn) {
-    const double a = 6378137.0, f = 1.0 / 298.257223563, k0 = 0.9996;
-    const double n = f / (2.0 - f), n2 = n * n, n3 = n2 * n, n4 = n3 * n, n5 = n4 * n, n6 = n5 * n;
-    const double A = a / (1.0 + n) * (1.0 + n2 / 4.0 + n4 / 64.0 + n6 / 256.0);
-    const double al[6] = {n / 2.0 - 2.0 * n2 / 3.0 + 5.0 * n3 / 16.0 + 41.0 * n4 / 180.0 - 127.0 * n5 / 288.0 +
-                              7891.0 * n6 / 37800.0,
-                          13.0 * n2 / 48.0 - 3.0 * n3 / 5.0 + 557.0 * n4 / 1440.0 + 281.0 * n5 / 630.0 -
-                              1983433.0 * n6 / 1935360.0,
-                          61.0 * n3 / 240.0 - 103.0 * n4 / 140.0 + 15061.0 * n5 / 26880.0 + 167603.0 * n6 / 181440.0,
-                          49561.0 * n4 / 161280.0 - 179.0 * n5 / 168.0 + 6601661.0 * n6 / 7257600.0,
-                          34729.0 * n5 / 80640.0 - 3418889.0 * n6 / 1995840.0,
-                          212378941.0 * n6 / 319334400.0};
-    const double deg = M_PI / 180.0;
-    const double phi = lat_deg * deg;
-    const double lam = (lon_deg - (6.0 * zone - 183.0)) * deg;
-    const double c = 2.0 * sqrt(n) / (1.0 + n);
-    const double t = sinh(atanh(sin(phi)) - c * atanh(c * sin(phi)));
-    const double xi = atan2(t, cos(lam));
-    const double eta = atanh(sin(lam) / sqrt(1.0 + t * t));
-    double se = eta, sn = xi;
-    for (int j = 1; j <= 6; ++j) {
-        se += al[j - 1] * cos(2.0 * j * xi) * sinh(2.0 * j * eta);
-        sn += al[j - 1] * sin(2.0 * j * xi) * cosh(2.0 * j * eta);
-    }
-    *e = 500000.0 + k0 * A * se;
-    *nn = (south ? 10000000.0 : 0.0) + k0 * A * sn;
-}
 
 __global__ void k_dsm_points(DsmPointArgs g) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;

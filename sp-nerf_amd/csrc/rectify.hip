@@ -8,8 +8,8 @@
 //    they arrive by scalar loads (eleven 64-B s_load per view in the ISA), not once per lane.
 //    HBM: 8 B of DSM per cell; per view and cell at most 16·C B of image (four pixels, mostly shared
 //    with the neighbouring cells through L2) and 4·C + 1 B out (+ 16 B of pix when asked for).
-//  * k_rectify_sample — the same read (sample_cell) at stored pixel positions.  sample_cell is
-//    compiled without fused multiply-adds (#pragma clang fp contract(off), honoured under the
+//  * k_rectify_sample — the same read (sample_cell of csrc/rectify_cell.h, which sweep.hip shares, as
+//    it does project_packed) at stored pixel positions.  sample_cell is compiled without fused multiply-adds (#pragma clang fp contract(off), honoured under the
 //    Makefile's -ffp-contract=fast-honor-pragmas), so the stated operation order is the result.
 //  * k_rectify_view_dirs — one workgroup per view, one thread per ground point (centre, four
 //    corners): project at alt_lo, localise at alt_hi (csrc/rpc.h), forward UTM, normalise.
@@ -18,48 +18,12 @@
 //    per-thread array, no scratch): V² compares of values that sit in L1.
 #include <cmath>
 
-#include "../../include/spnerf_amd_rectify.h"
-#include "rpc.h"
+#include "rectify_cell.h"
 #include "utm.h"
 
 namespace spn {
 
 constexpr int kRectifyThreads = 256;
-constexpr int kCam = SPNERF_RECTIFY_CAMERA_DOUBLES;
-
-// proj_n (csrc/rpc.h) on a packed camera, from degrees and metres to pixels
-__device__ __forceinline__ void project_packed(const double* __restrict__ c, double lat, double lon, double alt, double& col,
-                                               double& row) {
-    const double la = (lat - c[2]) / c[7], lo = (lon - c[3]) / c[8], al = (alt - c[4]) / c[9];
-    col = rpoly(c + 50, la, lo, al) / rpoly(c + 70, la, lo, al) * c[6] + c[1];
-    row = rpoly(c + 10, la, lo, al) / rpoly(c + 30, la, lo, al) * c[5] + c[0];
-}
-
-// the bilinear read of include/spnerf_amd_rectify.h; false (and NaN in every channel) outside the image
-__device__ __forceinline__ bool sample_cell(const spnerf_rectify_image im, int C, double col, double row, float* __restrict__ out) {
-#pragma clang fp contract(off)
-    const double xl = (double)(im.width - 1), yl = (double)(im.height - 1);
-    if (!(col >= 0.0 && col <= xl && row >= 0.0 && row <= yl)) {   // a NaN or an infinity fails a comparison
-        for (int c = 0; c < C; ++c) out[c] = NAN;
-        return false;
-    }
-    const double fx0 = floor(col), fy0 = floor(row);
-    const double fx = col - fx0, fy = row - fy0;
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const int x1 = x0 + 1 < im.width ? x0 + 1 : im.width - 1, y1 = y0 + 1 < im.height ? y0 + 1 : im.height - 1;
-    const float* r0 = im.pixels + (int64_t)y0 * im.width * C;
-    const float* r1 = im.pixels + (int64_t)y1 * im.width * C;
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
-    for (int c = 0; c < C; ++c) {
-        const double p00 = (double)r0[(int64_t)x0 * C + c], p01 = (double)r0[(int64_t)x1 * C + c];
-        const double p10 = (double)r1[(int64_t)x0 * C + c], p11 = (double)r1[(int64_t)x1 * C + c];
-        const double top = gx * p00 + fx * p01;
-        const double bot = gx * p10 + fx * p11;
-        out[c] = (float)(top * gy + bot * fy);
-    }
-    return true;
-}
-
 struct RectifyArgs {
     double xoff, ytop, res;
     int64_t cells;
@@ -214,16 +178,6 @@ __global__ __launch_bounds__(kRectifyThreads) void k_rectify_mosaic(const float*
         mosaic[cell * C + c] = (float)out;
     }
     spread[cell] = (float)sqrt(dev / (double)((int64_t)n * C));
-}
-
-static int32_t check_grid(const char* who, const spnerf_ortho_grid* g) {
-    SPN_ARG(g->xsize > 0 && g->ysize > 0, "%s: grid of %d x %d cells", who, g->xsize, g->ysize);
-    SPN_ARG((int64_t)g->xsize * g->ysize <= ((int64_t)1 << 32), "%s: grid of %d x %d cells is too large for one call", who, g->xsize,
-            g->ysize);
-    SPN_ARG(g->zone >= 1 && g->zone <= 60, "%s: UTM zone %d", who, g->zone);
-    SPN_ARG(g->resolution > 0.0 && std::isfinite(g->resolution), "%s: resolution %g", who, g->resolution);
-    SPN_ARG(std::isfinite(g->xoff) && std::isfinite(g->ytop), "%s: non-finite grid origin", who);
-    return SPNERF_OK;
 }
 
 static int32_t check_views(const char* who, int32_t n_views) {

@@ -30,6 +30,8 @@ from . import rectify  # noqa: F401  (camera images on the ground grid over a DS
 from .rectify import orthorectify  # noqa: F401
 from . import sweep  # noqa: F401  (a photo-consistency DSM from the camera images alone: grey planes, window ZNCC, the pick)
 from .sweep import plane_sweep  # noqa: F401
+from . import sgm  # noqa: F401  (the sweep's score volume regularised across cells: semi-global aggregation, then the pick)
+from .sgm import smooth_sweep  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

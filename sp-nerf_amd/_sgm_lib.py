@@ -1,0 +1,43 @@
+"""ctypes signatures of the semi-global aggregation exports (include/spnerf_amd_sgm.h), applied to the
+same libspnerf_amd.so handle as ``_lib.SIGNATURES``; errors come back through ``_lib.check``."""
+from __future__ import annotations
+
+from ctypes import POINTER, c_double, c_float, c_int32, c_int64, c_void_p
+
+from . import _lib
+
+SPNERF_SGM_ABI_VERSION = 1
+SGM_MAX_PLANES = 512
+SGM_TILE = 64
+
+# name → (restype, argtypes); the exact export list of include/spnerf_amd_sgm.h
+SIGNATURES = {
+    "spnerf_sgm_abi_version": (c_int32, []),
+    "spnerf_sgm_workspace_bytes": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "spnerf_sgm_aggregate": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_int32, c_void_p, c_void_p,
+                                       c_int64, c_void_p]),
+    "spnerf_sgm_pick": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+}
+
+_bound = False
+
+
+def lib():
+    """The library handle of ``_lib.lib()`` with the aggregation signatures applied (once).  A library
+    without these exports is an error: there is no fallback."""
+    global _bound
+    handle = _lib.lib()
+    if not _bound:
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:
+                raise _lib.SpnerfError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
+                                       "(`make -C sp-nerf_amd`)") from None
+            fn.restype = res
+            fn.argtypes = args
+        if handle.spnerf_sgm_abi_version() != SPNERF_SGM_ABI_VERSION:
+            raise _lib.SpnerfError("libspnerf_amd.so: semi-global aggregation ABI version mismatch, rebuild it")
+        _bound = True
+    return handle

@@ -8,8 +8,8 @@
 //    greys read through an accessor: global planes (k_sweep_score) or the LDS tile (k_sweep).  mu_v and
 //    sqrt(ss_v) live in arrays indexed by the fully unrolled view loop, i.e. in registers: the kernels are
 //    instantiated for VMAX = 4, 8 and 16 and views at or beyond V are predicated off.
-//  * Pick — the running best of a cell and the scores of its two neighbouring planes, fed plane by plane:
-//    from a stored volume (k_sweep_pick) or as the planes are scored (k_sweep).
+//  * Pick (csrc/sweep_pick.h) — the running best of a cell and the scores of its two neighbouring planes, fed
+//    plane by plane: from a stored volume (k_sweep_pick) or as the planes are scored (k_sweep).
 //  * k_sweep — one workgroup of 256 threads per 16 x 16 tile.  The inverse UTM of the (16 + 2r)² cells of tile
 //    and halo once, lat / lon kept in LDS.  Per plane: each wavefront takes runs of 64 halo cells of one
 //    view (the view is wavefront-uniform, so camera and image table arrive by scalar loads) and writes
@@ -23,6 +23,7 @@
 
 #include "../../include/spnerf_amd_sweep.h"
 #include "rectify_cell.h"
+#include "sweep_pick.h"
 #include "utm.h"
 
 namespace spn {
@@ -127,36 +128,6 @@ __device__ __forceinline__ float score_cell(const Greys& a, int V, int j0, int j
         }
     return (float)((acc - (double)m) / ((double)m * (double)(m - 1)));
 }
-
-// the pick of the header, fed the planes of one cell in order
-struct Pick {
-    float best = NAN, prev = NAN, below = NAN, above = NAN;
-    int index = -1, m = 0;
-    __device__ __forceinline__ void plane(int k, float s, int views) {
-        if (index >= 0 && k == index + 1) above = s;
-        if (s == s && (index < 0 || (double)s > (double)best)) {
-            best = s;
-            index = k;
-            below = prev;
-            above = NAN;
-            m = views;
-        }
-        prev = s;
-    }
-    __device__ __forceinline__ float altitude(int K, double alt_lo, double step) const {
-        if (index < 0) return NAN;
-        double off = 0.0;
-        if (index > 0 && index < K - 1 && below == below && above == above) {
-            const double sm = (double)below, s0 = (double)best, sp = (double)above;
-            const double den = (sm - 2.0 * s0) + sp;
-            if (den < 0.0) {
-                off = 0.5 * (sm - sp) / den;
-                off = off < -0.5 ? -0.5 : off > 0.5 ? 0.5 : off;
-            }
-        }
-        return (float)(alt_lo + ((double)index + off) * step);
-    }
-};
 
 struct SweepArgs {
     double xoff, ytop, res, alt_lo, step, min_std;

@@ -10,6 +10,13 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// the minimum over the 64 lanes, in every lane (exact, so the butterfly's order does not matter; no NaN expected)
+__device__ __forceinline__ float wave_fmin(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // inclusive prefix product / sum over lanes 0..63 (T = float or double: torch's CPU cumsum /
 // cumprod accumulate in double, at::acc_type<float, false>)
 template <typename T>

@@ -7,7 +7,8 @@
 //    two rows (column-major marches) or on one row (row-major ones) of a DSM that fits in L2: plain
 //    cached loads.  The march of a cell is a DDA along the major axis of the sun's azimuth; it stops
 //    as soon as no later step can change the outputs (the bound from hmax).  Latency-bound: two
-//    dependent loads and a dozen fp64 operations per step.
+//    dependent loads and a dozen fp64 operations per step.  The march itself is csrc/shadow_march.h's,
+//    shared with the visibility floor (occlusion.hip).
 //    Nothing is fused (#pragma clang fp contract(off), honoured under the Makefile's
 //    -ffp-contract=fast-honor-pragmas): every product and sum is rounded once, as the numpy statement
 //    (tests/shadow_numpy.py) rounds them, so floor(y) never flips against it.
@@ -17,23 +18,15 @@
 
 #include "../../include/spnerf_amd_shadow.h"
 #include "common.h"
+#include "shadow_march.h"
 
 namespace spn {
 
-constexpr int kShadowThreads = 256;
-constexpr int kShadowTileW = 64, kShadowTileH = kShadowThreads / kShadowTileW;   // a wavefront per row of the tile
-constexpr int kShadowMaxParts = 256;      // partial maxima: 2 KiB, reduced by the first wavefront of every cast workgroup
 constexpr int kShadowDirsPerLaunch = 32;  // the marches of a launch travel as kernel arguments
 
-static int hmax_parts(int64_t cells) {
+int hmax_parts(int64_t cells) {
     const int64_t nb = (cells + 4 * kShadowThreads - 1) / (4 * kShadowThreads);
     return (int)(nb < kShadowMaxParts ? nb : kShadowMaxParts);
-}
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 __global__ __launch_bounds__(kShadowThreads) void k_shadow_hmax(const double* __restrict__ dsm, int64_t cells,
@@ -54,12 +47,9 @@ __global__ __launch_bounds__(kShadowThreads) void k_shadow_hmax(const double* __
     }
 }
 
-// One direction's march, prepared on the host: axis 0 steps along the columns, 1 along the rows,
-// -1 takes no step (a = b = 0); sgn is the step's sign along that axis.
-struct ShadowDir {
-    double q, rho;
-    int32_t axis, sgn;
-};
+void launch_shadow_hmax(const double* dsm, int64_t cells, double* part, hipStream_t st) {
+    hipLaunchKernelGGL(k_shadow_hmax, dim3(hmax_parts(cells)), dim3(kShadowThreads), 0, st, dsm, cells, part);
+}
 
 struct ShadowArgs {
     const double* dsm;
@@ -71,20 +61,12 @@ struct ShadowArgs {
 };
 
 __global__ __launch_bounds__(kShadowThreads) void k_shadow_cast(ShadowArgs g) {
-#pragma clang fp contract(off)
     __shared__ double s_hmax;
     const int tid = threadIdx.x;
-    if (tid < 64) {
-        double v = -INFINITY;
-        for (int p = tid; p < g.nparts; p += 64) v = fmax(v, g.part[p]);
-        v = wave_max_f64(v);
-        if (tid == 0) s_hmax = v;
-    }
-    __syncthreads();
+    const double hmax = block_hmax(g.part, g.nparts, &s_hmax);
     const int i = (int)(blockIdx.x % g.tiles_x) * kShadowTileW + (tid & (kShadowTileW - 1));
     const int j = (int)(blockIdx.x / g.tiles_x) * kShadowTileH + tid / kShadowTileW;
     if (i >= g.W || j >= g.H) return;
-    const ShadowDir d = g.d[blockIdx.y];
     const int64_t cell = (int64_t)j * g.W + i;
     const int64_t o = (int64_t)blockIdx.y * g.H * g.W + cell;
     const double h = g.dsm[cell];
@@ -94,39 +76,7 @@ __global__ __launch_bounds__(kShadowThreads) void k_shadow_cast(ShadowArgs g) {
         return;
     }
     const bool want = g.excess != nullptr;
-    double run = -INFINITY;
-    if (d.axis >= 0) {
-        // major: the axis the march steps along; minor: the one it interpolates along
-        const int maj0 = d.axis ? j : i, min0 = d.axis ? i : j;
-        const int nmaj = d.axis ? g.H : g.W, nmin = d.axis ? g.W : g.H;
-        const int64_t smaj = d.axis ? g.W : 1, smin = d.axis ? 1 : g.W;
-        const double top = s_hmax - h, last = (double)(nmin - 1);
-        for (int m = 1;; ++m) {
-            const int c = maj0 + m * d.sgn;
-            if (c < 0 || c >= nmaj) break;
-            const double dm = (double)m;
-            const double drop = dm * d.rho;
-            // no step from m on exceeds top - drop; without `excess` a non-positive value changes nothing
-            const double bound = top - drop;
-            if (bound <= run || (!want && bound <= 0.0)) break;
-            const double y = (double)min0 + dm * d.q;
-            if (!(y >= 0.0 && y <= last)) break;   // y is monotone in m: it has left for good
-            const double fl = floor(y), f = y - fl;
-            const double* p = g.dsm + (int64_t)c * smaj + (int64_t)fl * smin;   // rows floor(y) [+ 1]: inside, see above
-            double hs = p[0];
-            if (f != 0.0) {   // then y < nmin - 1, so floor(y) + 1 is inside
-                const double h1 = p[smin];
-                if (hs != hs || h1 != h1) continue;
-                const double t = hs + f * (h1 - hs);
-                hs = fmin(fmax(t, fmin(hs, h1)), fmax(hs, h1));
-            } else if (hs != hs) {
-                continue;
-            }
-            const double e = (hs - h) - drop;
-            run = fmax(run, e);
-            if (!want && e > 0.0) break;
-        }
-    }
+    const double run = shadow_march(g.dsm, g.H, g.W, j, i, g.d[blockIdx.y], hmax, h, want);
     g.shadow[o] = run > 0.0 ? 1 : 0;
     if (want) g.excess[o] = run;
 }
@@ -250,7 +200,7 @@ extern "C" int32_t spnerf_shadow_cast(const double* dsm, int32_t height, int32_t
     SPN_ARG(tiles <= 0x7fffffffLL, "shadow_cast: grid of %d x %d cells is too large for one call", width, height);
     const int nparts = hmax_parts(cells);
     ProfScope prof("shadow", st, 0.0, (double)cells * (8.0 + n_dirs * (excess ? 9.0 : 1.0)));
-    hipLaunchKernelGGL(k_shadow_hmax, dim3(nparts), dim3(kShadowThreads), 0, st, dsm, cells, (double*)workspace);
+    launch_shadow_hmax(dsm, cells, (double*)workspace, st);
     SPN_HIP(hipGetLastError());
     for (int k0 = 0; k0 < n_dirs; k0 += kShadowDirsPerLaunch) {
         const int nk = n_dirs - k0 < kShadowDirsPerLaunch ? n_dirs - k0 : kShadowDirsPerLaunch;
@@ -259,20 +209,7 @@ extern "C" int32_t spnerf_shadow_cast(const double* dsm, int32_t height, int32_t
         g.shadow = shadow + (int64_t)k0 * cells;
         g.excess = excess ? excess + (int64_t)k0 * cells : nullptr;
         g.H = height; g.W = width; g.tiles_x = tiles_x;
-        for (int k = 0; k < nk; ++k) {
-            const float* s = dirs + 3 * (k0 + k);
-            const double a = (double)s[0], b = -(double)s[1], u = (double)s[2];
-            ShadowDir& d = g.d[k];
-            if (a == 0.0 && b == 0.0) {
-                d.axis = -1;
-            } else if (std::fabs(a) >= std::fabs(b)) {
-                d.axis = 0; d.sgn = a > 0.0 ? 1 : -1;
-                d.q = b / std::fabs(a); d.rho = resolution * u / std::fabs(a);
-            } else {
-                d.axis = 1; d.sgn = b > 0.0 ? 1 : -1;
-                d.q = a / std::fabs(b); d.rho = resolution * u / std::fabs(b);
-            }
-        }
+        for (int k = 0; k < nk; ++k) g.d[k] = shadow_dir(dirs + 3 * (k0 + k), resolution);
         hipLaunchKernelGGL(k_shadow_cast, dim3((unsigned)tiles, (unsigned)nk), dim3(kShadowThreads), 0, st, g);
         SPN_HIP(hipGetLastError());
     }

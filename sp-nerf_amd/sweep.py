@@ -7,7 +7,8 @@ the views are scored against each other around each cell — the mean pairwise z
 cross-correlation of their grey windows — and the best plane per cell is kept, refined by a parabola
 through its two neighbours.  The header states every operation and its order; ``plane_grey``,
 ``window_score`` and ``pick_plane`` are the three steps on their own, and the fused call has their
-bytes.  Occlusion is not modelled, as in any plane sweep.
+bytes.  Occlusion is not modelled, as in any plane sweep; ``occlusion.visible_sweep`` is this sweep with the
+views gated by a visibility floor from a prior DSM.
 
 Conventions are ``rectify``'s: cameras are ``rectify.Camera``s, an image is a device tensor
 (h, w, C) float32 with C <= 4, the planes lie in the ``GroundGrid`` layout (row 0 the northernmost).

@@ -6,7 +6,7 @@
 //    the reference height 0 with the early stop of the cast's `excess` path: hmax from the partial maxima
 //    that shadow.hip's reduction leaves in the workspace.  The cell's own height is not read.
 //  * k_occlusion_gate — one thread per (view, cell) of a stored grey / valid pair, in place.
-//  * k_sweep<VMAX, true> — csrc/sweep_cell.h's fused sweep with the floors of tile and halo in LDS.  LDS and
+//  * k_sweep<VMAX, true, false> — csrc/sweep_cell.h's fused sweep with the floors of tile and halo in LDS.  LDS and
 //    not registers: the lane ↔ (view, halo cell) assignment is the same at every plane, but a lane owns up to
 //    VMAX·9/4 = 36 entries at V = 16, r = 4, which would need a fully unrolled, predicated item loop and 36
 //    more VGPRs on a 132-VGPR kernel (3 → 2 waves per SIMD), where 4·V·(16 + 2r)² B of LDS cost nothing at the

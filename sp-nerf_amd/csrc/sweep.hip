@@ -2,8 +2,9 @@
 // images alone.  The whole translation unit is compiled without fused multiply-adds (the file-scope
 // pragma below, honoured under the Makefile's -ffp-contract=fast-honor-pragmas), so the header's
 // operation order is the result and a device function gives the same bits in every kernel that uses it.
-//  * grey_cell, score_cell<VMAX> and the fused k_sweep<VMAX, GATED> are csrc/sweep_cell.h's, shared with the
-//    sweep gated by a visibility floor (occlusion.hip); this file instantiates the ungated k_sweep.
+//  * grey_cell, score_cell<VMAX> and the fused k_sweep<VMAX, GATED, SURFACE> are csrc/sweep_cell.h's, shared with the
+//    sweep gated by a visibility floor (occlusion.hip) and the sweep around a base surface (surface.hip); this file
+//    instantiates the plain k_sweep.
 //  * Pick (csrc/sweep_pick.h) — the running best of a cell and the scores of its two neighbouring planes, fed
 //    plane by plane: from a stored volume (k_sweep_pick) or as the planes are scored (k_sweep).
 //  * k_sweep_grey, k_sweep_score, k_sweep_pick — the staged path, one thread per cell each.

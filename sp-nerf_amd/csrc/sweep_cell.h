@@ -1,6 +1,7 @@
 // The device functions and the fused kernel of the plane sweep (include/spnerf_amd_sweep.h), shared by
-// sweep.hip (the ungated instances) and occlusion.hip (the instances gated by a visibility floor,
-// include/spnerf_amd_occlusion.h).  A translation unit includes this under a file-scope
+// sweep.hip (the ungated instances), occlusion.hip (the instances gated by a visibility floor,
+// include/spnerf_amd_occlusion.h) and surface.hip (the instances around a base surface,
+// include/spnerf_amd_surface.h).  A translation unit includes this under a file-scope
 // `#pragma clang fp contract(off)`: the header's operation order is the result, and a device function
 // gives the same bits in every kernel that uses it.
 //  * grey_cell — one (view, cell) at one altitude: project_packed, sample_cell (csrc/rectify_cell.h), the
@@ -9,14 +10,17 @@
 //    greys read through an accessor: global planes (k_sweep_score) or the LDS tile (k_sweep).  mu_v and
 //    sqrt(ss_v) live in arrays indexed by the fully unrolled view loop, i.e. in registers: the kernels are
 //    instantiated for VMAX = 4, 8 and 16 and views at or beyond V are predicated off.
-//  * k_sweep<VMAX, GATED> — one workgroup of 256 threads per 16 x 16 tile.  The inverse UTM of the
+//  * k_sweep<VMAX, GATED, SURFACE> — one workgroup of 256 threads per 16 x 16 tile.  The inverse UTM of the
 //    (16 + 2r)² cells of tile and halo once, lat / lon kept in LDS.  Per plane: each wavefront takes runs of
 //    64 halo cells of one view (the view is wavefront-uniform, so camera and image table arrive by scalar
 //    loads) and writes grey[v][halo cell] to LDS, NaN standing for invalid; barrier; each thread scores its
 //    own cell from LDS; barrier.  LDS: 16·side² B of lat / lon + 4·V·side² B of greys, 45 KB at r = 4,
 //    V = 16.  GATED: the floors of tile and halo are read once, into 4·V·side² B more of LDS, and a lane
 //    whose (view, halo cell) is gated at the plane writes NaN without projecting or reading the image; the
-//    projection sits in a divergent region, which a wavefront with no live lane branches over.
+//    projection sits in a divergent region, which a wavefront with no live lane branches over.  SURFACE
+//    (include/spnerf_amd_surface.h): plane k is the surface base + (alt_lo + k·step); the bases of tile and halo
+//    are read once, into 4·side² B more of LDS, NaN outside the grid, and a lane whose base is not finite writes
+//    NaN the same way.  `prior` is the floor of a GATED instance and the base of a SURFACE one; no instance is both.
 #pragma once
 #include <cmath>
 
@@ -141,14 +145,18 @@ __device__ __forceinline__ void tile_origin(unsigned b, int tx, int& tj0, int& t
     ti0 = (int)(b % (unsigned)tx) * kTile;
 }
 
-// dynamic LDS: lat [hc], lon [hc] fp64, then grey [V][hc] fp32 and, GATED, floor [V][hc] fp32; hc = (kTile + 2·radius)².
-// GATED: view v at a cell is invalid at plane k when (alt_k + slack) < (double)floor[v][cell], floor [V][ysize][xsize] fp32.
-template <int VMAX, bool GATED>
+// dynamic LDS: lat [hc], lon [hc] fp64, then grey [V][hc] fp32 and, GATED, floor [V][hc] fp32 or, SURFACE, base [hc] fp32;
+// hc = (kTile + 2·radius)².
+// GATED: view v at a cell is invalid at plane k when (alt_k + slack) < (double)prior[v][cell], prior [V][ysize][xsize] fp32.
+// SURFACE: the altitude of a cell at plane k is (double)prior[cell] + alt_k, prior [ysize][xsize] fp32, every view invalid
+// where that base is not finite; the picked altitude is lifted by the cell's base, (float)((double)base + (double)altitude).
+template <int VMAX, bool GATED, bool SURFACE>
 __global__ __launch_bounds__(kSweepThreads) void k_sweep(SweepArgs g, int tx, const double* __restrict__ cams,
                                                          const spnerf_rectify_image* __restrict__ images, float* __restrict__ altitude,
                                                          float* __restrict__ score, int32_t* __restrict__ index,
                                                          uint8_t* __restrict__ views, float* __restrict__ volume,
-                                                         const float* __restrict__ floor, double slack) {
+                                                         const float* __restrict__ prior, double slack) {
+    static_assert(!(GATED && SURFACE), "a gated surface sweep is not there");
     extern __shared__ double s_mem[];
     const int r = g.radius, side = kTile + 2 * r, hc = side * side;
     double* s_lat = s_mem;
@@ -167,15 +175,24 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(SweepArgs g, int tx, co
         s_lat[h] = lat;
         s_lon[h] = lon;
     }
-    float* s_floor = s_grey + g.V * hc;
+    float* s_prior = s_grey + g.V * hc;
     if constexpr (GATED) {
         // the floors of tile and halo, once for all planes; outside the grid NaN, which gates nothing (and lat is NaN there)
         for (int e = tid; e < g.V * hc; e += kSweepThreads) {
             const int v = e / hc, h = e - v * hc;
             const int j = tj0 - r + h / side, i = ti0 - r + h % side;
             float f = NAN;
-            if (j >= 0 && j < g.ysize && i >= 0 && i < g.xsize) f = floor[((int64_t)v * g.ysize + j) * g.xsize + i];
-            s_floor[e] = f;
+            if (j >= 0 && j < g.ysize && i >= 0 && i < g.xsize) f = prior[((int64_t)v * g.ysize + j) * g.xsize + i];
+            s_prior[e] = f;
+        }
+    }
+    if constexpr (SURFACE) {
+        // the bases of tile and halo, once for all planes; outside the grid NaN (and lat is NaN there)
+        for (int h = tid; h < hc; h += kSweepThreads) {
+            const int j = tj0 - r + h / side, i = ti0 - r + h % side;
+            float b = NAN;
+            if (j >= 0 && j < g.ysize && i >= 0 && i < g.xsize) b = prior[(int64_t)j * g.xsize + i];
+            s_prior[h] = b;
         }
     }
     __syncthreads();
@@ -200,10 +217,16 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(SweepArgs g, int tx, co
                 const double lat = s_lat[h];
                 float grey = NAN;
                 bool live = lat == lat;
-                if constexpr (GATED) live = live && !(reach < (double)s_floor[v * hc + h]);   // a NaN floor gates nothing
+                if constexpr (GATED) live = live && !(reach < (double)s_prior[v * hc + h]);   // a NaN floor gates nothing
+                double at = alt;
+                if constexpr (SURFACE) {
+                    const float b = s_prior[h];
+                    live = live && isfinite(b);
+                    at = (double)b + alt;
+                }
                 if (live) {
                     bool ok;
-                    grey = grey_cell(cams + (int64_t)v * kCam, images[v], g.C, lat, s_lon[h], alt, ok);
+                    grey = grey_cell(cams + (int64_t)v * kCam, images[v], g.C, lat, s_lon[h], at, ok);
                     if (!ok) grey = NAN;
                 }
                 s_grey[v * hc + h] = grey;
@@ -219,7 +242,9 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep(SweepArgs g, int tx, co
         __syncthreads();   // the next plane overwrites the greys
     }
     if (mine) {
-        altitude[cell] = p.altitude(g.K, g.alt_lo, g.step);
+        float a = p.altitude(g.K, g.alt_lo, g.step);
+        if constexpr (SURFACE) a = (float)((double)s_prior[(tid / kTile + r) * side + tid % kTile + r] + (double)a);
+        altitude[cell] = a;
         score[cell] = p.best;
         index[cell] = p.index;
         views[cell] = (uint8_t)p.m;
@@ -262,12 +287,13 @@ static double score_flop(int V, int radius) {
 }
 
 // The fused launch of both translation units: the arguments checked as spnerf_sweep states them, the
-// instance chosen by the view count.  `floor` and `slack` are read by the gated instances only.
-template <bool GATED>
+// instance chosen by the view count.  `prior` is the floor [V][ysize][xsize] of the gated instances and the base
+// [ysize][xsize] of the surface instances; `slack` is read by the gated instances only.
+template <bool GATED, bool SURFACE = false>
 static int32_t launch_sweep(const char* who, const spnerf_ortho_grid* grid, const double* cameras, const spnerf_rectify_image* images,
                             int32_t n_views, int32_t channels, double alt_lo, double step, int32_t n_planes, int32_t radius,
                             int32_t min_views, double min_std, float* altitude, float* score, int32_t* index, uint8_t* views,
-                            float* volume, const float* floor, double slack, hipStream_t st) {
+                            float* volume, const float* prior, double slack, hipStream_t st) {
     SPN_TRY(check_grid(who, grid));
     SPN_TRY(check_views_channels(who, n_views, channels));
     SPN_TRY(check_planes(who, n_planes, alt_lo, step));
@@ -279,21 +305,22 @@ static int32_t launch_sweep(const char* who, const spnerf_ortho_grid* grid, cons
     int tx;
     const unsigned tiles = tiles_of(g.ysize, g.xsize, tx);
     const int side = kTile + 2 * radius, hc = side * side;
-    // ungated at most 46,080 B; gated at most 82,944 B, above the 64 KiB a launch gets unasked
-    const size_t lds = (size_t)hc * (16 + (GATED ? 8 : 4) * (size_t)n_views);
+    // ungated at most 46,080 B, a surface sweep 2,304 B more; gated at most 82,944 B, above the 64 KiB a launch gets unasked
+    const size_t lds = (size_t)hc * (16 + (GATED ? 8 : 4) * (size_t)n_views + (SURFACE ? 4 : 0));
     const double cells = (double)g.xsize * g.ysize;
     ProfScope prof(who, st, (double)n_planes * ((double)tiles * hc * n_views * grey_flop(channels) + cells * score_flop(n_views, radius)),
-                   cells * (13.0 + (volume ? 4.0 * n_planes : 0.0)) + (GATED ? 4.0 * (double)tiles * hc * n_views : 0.0));
+                   cells * (13.0 + (volume ? 4.0 * n_planes : 0.0)) + (GATED ? 4.0 * (double)tiles * hc * n_views : 0.0) +
+                       (SURFACE ? 4.0 * (double)tiles * hc : 0.0));
     auto launch = [&](auto kernel) -> int32_t {
         if (lds > 65536) SPN_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kernel, dim3(tiles), dim3(kSweepThreads), lds, st, g, tx, cameras, images, altitude, score, index, views, volume,
-                           floor, slack);
+                           prior, slack);
         SPN_HIP(hipGetLastError());
         return SPNERF_OK;
     };
-    if (n_views <= 4) return launch(k_sweep<4, GATED>);
-    if (n_views <= 8) return launch(k_sweep<8, GATED>);
-    return launch(k_sweep<16, GATED>);
+    if (n_views <= 4) return launch(k_sweep<4, GATED, SURFACE>);
+    if (n_views <= 8) return launch(k_sweep<8, GATED, SURFACE>);
+    return launch(k_sweep<16, GATED, SURFACE>);
 }
 
 }  // namespace spn

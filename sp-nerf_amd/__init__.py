@@ -36,6 +36,8 @@ from . import occlusion  # noqa: F401  (the sweep's views gated by a visibility 
 from .occlusion import gate_plane, refine_sweep, visibility_floor, visible_sweep  # noqa: F401
 from . import surface  # noqa: F401  (the sweep around a base surface instead of horizontal planes, and the coarse-to-fine chain)
 from .surface import coarsen, pyramid_sweep, surface_grey, surface_lift, surface_sweep, upsample_dsm  # noqa: F401
+from . import dsm_view  # noqa: F401  (a ground-grid DSM seen from a camera: the cast, rasters read at the hits, depth priors)
+from .dsm_view import dsm_depth_priors, hit_ecef, normalised_depth, sample_at, view_dsm  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

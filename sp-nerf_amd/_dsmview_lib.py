@@ -1,0 +1,43 @@
+"""ctypes signatures of the DSM-view exports (include/spnerf_amd_dsmview.h), applied to the same
+libspnerf_amd.so handle as ``_lib.SIGNATURES``; errors come back through ``_lib.check``."""
+from __future__ import annotations
+
+from ctypes import POINTER, c_double, c_int32, c_int64, c_void_p
+
+from . import _lib
+from ._ortho_lib import OrthoGrid
+
+SPNERF_DSMVIEW_ABI_VERSION = 1
+DSMVIEW_NEAREST, DSMVIEW_BILINEAR = 0, 1
+
+# name → (restype, argtypes); the exact export list of include/spnerf_amd_dsmview.h
+SIGNATURES = {
+    "spnerf_dsmview_abi_version": (c_int32, []),
+    "spnerf_dsmview_workspace_bytes": (c_int64, [c_int32, c_int32]),
+    "spnerf_dsmview_cast": (c_int32, [POINTER(OrthoGrid), c_void_p, c_void_p, c_double, c_double, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "spnerf_dsmview_sample": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "spnerf_dsmview_ecef": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+}
+
+_bound = False
+
+
+def lib():
+    """The library handle of ``_lib.lib()`` with the DSM-view signatures applied (once).  A library
+    without these exports is an error: there is no fallback."""
+    global _bound
+    handle = _lib.lib()
+    if not _bound:
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:
+                raise _lib.SpnerfError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
+                                       "(`make -C sp-nerf_amd`)") from None
+            fn.restype = res
+            fn.argtypes = args
+        if handle.spnerf_dsmview_abi_version() != SPNERF_DSMVIEW_ABI_VERSION:
+            raise _lib.SpnerfError("libspnerf_amd.so: DSM-view ABI version mismatch, rebuild it")
+        _bound = True
+    return handle

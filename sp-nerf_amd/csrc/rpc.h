@@ -48,21 +48,24 @@ __device__ __forceinline__ void proj_n(const RpcCam& a, double lat, double lon, 
     row = rpoly(a.rn, lat, lon, alt) / rpoly(a.rd, lat, lon, alt);
 }
 
-// normalised image (cn, rn) at normalised altitude an → degrees (lon, lat)
-__device__ inline void localize(const RpcCam& a, double cn, double rn, double an, double& lon_d, double& lat_d) {
+// The iteration itself, over any projection proj(lat, lon, an, col, row) on normalised coordinates: normalised
+// image (cn, rn) at normalised altitude an → normalised (lon, lat).  Stated once: localize below runs it on an
+// RpcCam, csrc/dsm_view.hip on a packed camera table.
+template <class Proj>
+__device__ __forceinline__ void localize_n(Proj proj, double cn, double rn, double an, double& lon_n, double& lat_n) {
     double lon = -1.0, lat = -1.0, eps = 2.0;
     int extra = -1;
     for (int it = 0; it <= 100; ++it) {
         double x0, y0;
-        proj_n(a, lat, lon, an, x0, y0);
+        proj(lat, lon, an, x0, y0);
         const double res = (x0 - cn) * (x0 - cn) + (y0 - rn) * (y0 - rn);
         if (res < 1e-18) {
             if (extra < 0) extra = 2;
             if (extra-- == 0) break;
         }
         double x1, y1, x2, y2;
-        proj_n(a, lat, lon + eps, an, x1, y1);
-        proj_n(a, lat + eps, lon, an, x2, y2);
+        proj(lat, lon + eps, an, x1, y1);
+        proj(lat + eps, lon, an, x2, y2);
         const double e1x = x1 - x0, e1y = y1 - y0, e2x = x2 - x0, e2y = y2 - y0;
         const double ux = cn - x0, uy = rn - y0;
         const double a1 = (ux * e1x + uy * e1y) / (e1x * e1x + e1y * e1y);
@@ -71,6 +74,14 @@ __device__ inline void localize(const RpcCam& a, double cn, double rn, double an
         lat += a2 * eps;
         eps = 0.1;
     }
+    lon_n = lon;
+    lat_n = lat;
+}
+
+// normalised image (cn, rn) at normalised altitude an → degrees (lon, lat)
+__device__ inline void localize(const RpcCam& a, double cn, double rn, double an, double& lon_d, double& lat_d) {
+    double lon, lat;
+    localize_n([&a](double la, double lo, double al, double& x, double& y) { proj_n(a, la, lo, al, x, y); }, cn, rn, an, lon, lat);
     lon_d = lon * a.off[8] + a.off[3];
     lat_d = lat * a.off[7] + a.off[2];
 }

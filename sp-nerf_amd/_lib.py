@@ -115,11 +115,28 @@ SIGNATURES = {
     "spnerf_grad_mark_query": (c_int32, [c_int32, c_int32]),
 }
 
+# every module that binds a further header's table to the same handle (each ends with `lib = bind(...)`);
+# a new header adds its module here, and tests/test_abi_tables.py then covers it
+BINDING_MODULES = ("_eval_lib", "_view_lib", "_image_lib", "_loss_lib", "_data_lib", "_lpips_lib", "_val_lib",
+                   "_train_lib", "_dp_lib", "_relight_lib", "_ortho_lib", "_shadow_lib", "_rectify_lib", "_sweep_lib",
+                   "_sgm_lib", "_occlusion_lib", "_surface_lib", "_dsmview_lib")
+
 _lib = None
 
 
 class SpnerfError(RuntimeError):
     pass
+
+
+def _apply(handle, signatures) -> None:
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:
+            raise SpnerfError(f"{LIB_PATH} does not export {name}: rebuild it "
+                              "(`make -C sp-nerf_amd`)") from None
+        fn.restype = res
+        fn.argtypes = args
 
 
 def lib():
@@ -130,12 +147,28 @@ def lib():
             raise SpnerfError(f"{LIB_PATH} is missing: build it with `make -C sp-nerf_amd` "
                               "(or __graft_entry__.build()); there is no CPU fallback")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
+        _apply(handle, SIGNATURES)
         _lib = handle
     return _lib
+
+
+def bind(signatures, version_symbol: str, version: int, what: str):
+    """The ``lib()`` of one further header: nothing is loaded here; the returned function gives the
+    handle of ``lib()`` with ``signatures`` applied and the header's ABI version checked (once).  A
+    library without these exports is an error: there is no fallback."""
+    bound = False
+
+    def bound_lib():
+        nonlocal bound
+        handle = lib()
+        if not bound:
+            _apply(handle, signatures)
+            if getattr(handle, version_symbol)() != version:
+                raise SpnerfError(f"libspnerf_amd.so: {what} ABI version mismatch, rebuild it")
+            bound = True
+        return handle
+
+    return bound_lib
 
 
 def check(rc: int, what: str = "") -> None:

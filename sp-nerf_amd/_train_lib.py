@@ -39,24 +39,4 @@ SIGNATURES = {
                                                 c_void_p, POINTER(_lib.Rng), c_void_p]),
 }
 
-_bound = False
-
-
-def lib():
-    """The library handle of ``_lib.lib()`` with the training-step signatures applied (once).  A
-    library without these exports is an error: there is no fallback."""
-    global _bound
-    handle = _lib.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError:
-                raise _lib.SpnerfError(f"{_lib.LIB_PATH} does not export {name}: rebuild it "
-                                       "(`make -C sp-nerf_amd`)") from None
-            fn.restype = res
-            fn.argtypes = args
-        if handle.spnerf_train_abi_version() != SPNERF_TRAIN_ABI_VERSION:
-            raise _lib.SpnerfError("libspnerf_amd.so: training-step ABI version mismatch, rebuild it")
-        _bound = True
-    return handle
+lib = _lib.bind(SIGNATURES, "spnerf_train_abi_version", SPNERF_TRAIN_ABI_VERSION, "training-step")

@@ -75,6 +75,9 @@ typedef __bf16 bf16;
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 __host__ __device__ inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// the workgroups of `threads` that cover n entries, one thread each; a byte count rounded up to 16
+inline unsigned blocks_of(int64_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // 4 consecutive activations as fp32 (the MLP keeps activations in fp32 or bf16, cfg.dtype)
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }

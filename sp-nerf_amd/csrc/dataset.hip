@@ -31,12 +31,12 @@ __device__ __forceinline__ float mul_then_add(float a, float x, float b) {
 __device__ __forceinline__ float nan_min(float a, float b) { return (a < b || a != a) ? a : b; }
 __device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
 
-__device__ __forceinline__ float wave_min(float v) {
+__device__ __forceinline__ float wave_nan_min(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = nan_min(v, __shfl_xor(v, off, 64));
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+__device__ __forceinline__ float wave_nan_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = nan_max(v, __shfl_xor(v, off, 64));
     return v;
@@ -45,8 +45,8 @@ __device__ __forceinline__ float wave_max(float v) {
 // (min, max) over the block, in every thread
 __device__ __forceinline__ void block_range(float& lo, float& hi) {
     __shared__ float s_lo[kWaves], s_hi[kWaves];
-    lo = wave_min(lo);
-    hi = wave_max(hi);
+    lo = wave_nan_min(lo);
+    hi = wave_nan_max(hi);
     if ((threadIdx.x & 63) == 0) {
         s_lo[threadIdx.x >> 6] = lo;
         s_hi[threadIdx.x >> 6] = hi;
@@ -142,8 +142,8 @@ __global__ __launch_bounds__(kBlock) void k_depth_priors(DepthArgs a) {
             if (depth == depth) dlo = dhi = depth;
         }
     }
-    dlo = wave_min(dlo);
-    dhi = wave_max(dhi);
+    dlo = wave_nan_min(dlo);
+    dhi = wave_nan_max(dhi);
     if ((threadIdx.x & 63) == 0 && dlo <= dhi) {
         atomic_min_f32(a.depth_range, dlo);
         atomic_max_f32(a.depth_range + 1, dhi);
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(kBlock) void k_scene_bounds(BoundsArgs a) {
         }
     }
     for (int j = 0; j < 3; ++j) {
-        lo[j] = wave_min(lo[j]);
-        hi[j] = wave_max(hi[j]);
+        lo[j] = wave_nan_min(lo[j]);
+        hi[j] = wave_nan_max(hi[j]);
     }
     if ((threadIdx.x & 63) == 0)
         for (int j = 0; j < 3; ++j)

@@ -32,6 +32,7 @@
 
 #include "../../include/spnerf_amd_eval.h"
 #include "common.h"
+#include "wave.h"
 
 namespace spn {
 
@@ -40,12 +41,6 @@ constexpr int kRegPix = 16;         // pixels of the tile per lane (32·32 / 64)
 constexpr int kRegWaves = 4;
 constexpr int kRegMaxShifts = (2 * SPNERF_EVAL_DSM_MAX_IRANGE + 1) * (2 * SPNERF_EVAL_DSM_MAX_IRANGE + 1);
 constexpr int kErrBlocks = (SPNERF_EVAL_DSM_SUMS_DOUBLES - 2) / 2;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_dsm_pivot(const double* u, const double* v, int n, double* pivot) {
     __shared__ int s_first[2];
@@ -153,12 +148,12 @@ __global__ __launch_bounds__(256) void k_dsm_ncc_moments(NccArgs g) {
             svv += b * b;
             suv += a * b;
         }
-        n = wave_sum_f64(n);
-        su = wave_sum_f64(su);
-        sv = wave_sum_f64(sv);
-        suu = wave_sum_f64(suu);
-        svv = wave_sum_f64(svv);
-        suv = wave_sum_f64(suv);
+        n = wave_sum(n);
+        su = wave_sum(su);
+        sv = wave_sum(sv);
+        suu = wave_sum(suu);
+        svv = wave_sum(svv);
+        suv = wave_sum(suv);
         if (lane < 6) {
             const double o = lane == 0 ? n : lane == 1 ? su : lane == 2 ? sv : lane == 3 ? suu : lane == 4 ? svv : suv;
             g.partial[(blk * S + s) * 6 + lane] = o;
@@ -288,8 +283,8 @@ __global__ __launch_bounds__(256) void k_dsm_apply_shift_err(ApplyArgs g) {
         }
     }
     if (!g.sums) return;
-    sum = wave_sum_f64(sum);
-    cnt = wave_sum_f64(cnt);
+    sum = wave_sum(sum);
+    cnt = wave_sum(cnt);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         s_part[wave][0] = sum;

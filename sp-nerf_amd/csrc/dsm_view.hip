@@ -21,6 +21,7 @@
 #include "../../include/spnerf_amd_dsmview.h"
 #include "rectify_cell.h"
 #include "utm.h"
+#include "wave.h"
 
 namespace spn {
 
@@ -34,12 +35,6 @@ static int view_parts(int64_t cells) {
     return (int)(nb < kViewMaxParts ? nb : kViewMaxParts);
 }
 
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(kViewThreads) void k_dsmview_hmax(const float* __restrict__ dsm, int64_t cells, float* __restrict__ part) {
     __shared__ float s_max[kViewThreads / 64];
     const int tid = threadIdx.x;
@@ -48,27 +43,13 @@ __global__ __launch_bounds__(kViewThreads) void k_dsmview_hmax(const float* __re
         const float x = dsm[c];
         if (fabsf(x) < INFINITY) v = fmaxf(v, x);
     }
-    v = wave_max_f32(v);
+    v = wave_max(v);
     if ((tid & 63) == 0) s_max[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < kViewThreads / 64; ++w) v = fmaxf(v, s_max[w]);
         part[blockIdx.x] = v;
     }
-}
-
-// The iteration of csrc/rpc.h (localize_n, the one spnerf_rpc_rays runs) over the projection of a packed camera
-// c: normalised image (cn, rn) at the normalised altitude an -> degrees (lat, lon).
-__device__ __forceinline__ void proj_packed_n(const double* __restrict__ c, double lat, double lon, double an, double& x, double& y) {
-    x = rpoly(c + 50, lat, lon, an) / rpoly(c + 70, lat, lon, an);
-    y = rpoly(c + 10, lat, lon, an) / rpoly(c + 30, lat, lon, an);
-}
-
-__device__ __forceinline__ void localize_packed(const double* __restrict__ c, double cn, double rn, double an, double& lat_d, double& lon_d) {
-    double lon, lat;
-    localize_n([c](double la, double lo, double al, double& x, double& y) { proj_packed_n(c, la, lo, al, x, y); }, cn, rn, an, lon, lat);
-    lon_d = lon * c[8] + c[3];
-    lat_d = lat * c[7] + c[2];
 }
 
 struct ViewArgs {
@@ -121,7 +102,7 @@ __global__ __launch_bounds__(kViewThreads) void k_dsmview_cast(ViewArgs g) {
     if (tid < 64) {
         float v = -INFINITY;
         for (int p = tid; p < g.nparts; p += 64) v = fmaxf(v, g.part[p]);
-        v = wave_max_f32(v);
+        v = wave_max(v);
         if (tid == 0) s_hmax = v;
     }
     __syncthreads();
@@ -262,15 +243,6 @@ __global__ __launch_bounds__(kViewThreads) void k_dsmview_ecef(const double* __r
     out[3 * k + 2] = z;
 }
 
-static unsigned view_blocks(int64_t n) { return (unsigned)((n + kViewThreads - 1) / kViewThreads); }
-static size_t view_align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-static int32_t check_cells(const char* who, int32_t ysize, int32_t xsize) {
-    SPN_ARG(xsize > 0 && ysize > 0, "%s: grid of %d x %d cells", who, xsize, ysize);
-    SPN_ARG((int64_t)xsize * ysize <= ((int64_t)1 << 32), "%s: grid of %d x %d cells is too large for one call", who, xsize, ysize);
-    return SPNERF_OK;
-}
-
 }  // namespace spn
 
 using namespace spn;
@@ -279,7 +251,7 @@ extern "C" int32_t spnerf_dsmview_abi_version(void) { return SPNERF_DSMVIEW_ABI_
 
 extern "C" int64_t spnerf_dsmview_workspace_bytes(int32_t ysize, int32_t xsize) {
     SPN_TRY(check_cells("dsmview_workspace_bytes", ysize, xsize));
-    return (int64_t)view_align16((size_t)view_parts((int64_t)ysize * xsize) * sizeof(float));
+    return (int64_t)align16((size_t)view_parts((int64_t)ysize * xsize) * sizeof(float));
 }
 
 extern "C" int32_t spnerf_dsmview_cast(const spnerf_ortho_grid* grid, const float* dsm, const double* camera, double alt_lo,
@@ -324,7 +296,7 @@ extern "C" int32_t spnerf_dsmview_sample(const float* raster, int32_t ysize, int
     SPN_ARG(mode == SPNERF_DSMVIEW_NEAREST || mode == SPNERF_DSMVIEW_BILINEAR, "dsmview_sample: mode %d is neither nearest (0) nor bilinear (1)",
             mode);
     ProfScope prof("dsmview_sample", st, (double)count * 16.0, (double)count * 28.0);
-    hipLaunchKernelGGL(k_dsmview_sample, dim3(view_blocks(count)), dim3(kViewThreads), 0, st, raster, ysize, xsize, cell, count, mode, out);
+    hipLaunchKernelGGL(k_dsmview_sample, dim3(blocks_of(count, kViewThreads)), dim3(kViewThreads), 0, st, raster, ysize, xsize, cell, count, mode, out);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -336,7 +308,7 @@ extern "C" int32_t spnerf_dsmview_ecef(const double* ground, const float* altitu
     SPN_ARG(count >= 1 && count <= ((int64_t)1 << 32), "dsmview_ecef: count %lld outside [1, 2^32]", (long long)count);
     SPN_ARG(zone >= 1 && zone <= 60, "dsmview_ecef: UTM zone %d", zone);
     ProfScope prof("dsmview_ecef", st, (double)count * 400.0, (double)count * 44.0);
-    hipLaunchKernelGGL(k_dsmview_ecef, dim3(view_blocks(count)), dim3(kViewThreads), 0, st, ground, altitude, count, zone, south ? 1 : 0,
+    hipLaunchKernelGGL(k_dsmview_ecef, dim3(blocks_of(count, kViewThreads)), dim3(kViewThreads), 0, st, ground, altitude, count, zone, south ? 1 : 0,
                        ecef_out);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;

@@ -56,8 +56,6 @@ __global__ __launch_bounds__(kGateThreads) void k_occlusion_gate(float* __restri
     }
 }
 
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 static int32_t check_dsm_grid(const char* who, int32_t height, int32_t width) {
     SPN_ARG(height > 0 && width > 0, "%s: grid of %d x %d cells", who, width, height);
     SPN_ARG(height <= (1 << 30) && width <= (1 << 30) && (int64_t)height * width <= ((int64_t)1 << 32),

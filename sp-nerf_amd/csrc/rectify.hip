@@ -191,8 +191,6 @@ static int32_t check_channels(const char* who, int32_t channels) {
     return SPNERF_OK;
 }
 
-static unsigned blocks_of(int64_t cells) { return (unsigned)((cells + kRectifyThreads - 1) / kRectifyThreads); }
-
 // spnerf_rectify_project (images NULL) and spnerf_rectify
 static int32_t launch_rectify(const char* who, const double* dsm, const spnerf_ortho_grid* grid, const double* cameras,
                               const spnerf_rectify_image* images, int32_t n_views, int32_t channels, float* rgb, uint8_t* valid,
@@ -206,7 +204,7 @@ static int32_t launch_rectify(const char* who, const double* dsm, const spnerf_o
     g.xsize = grid->xsize; g.zone = grid->zone; g.south = grid->south ? 1 : 0; g.V = n_views; g.C = channels;
     const double per_view = (images ? 20.0 * channels + 1.0 : 0.0) + (pix ? 16.0 : 0.0);
     ProfScope prof("rectify", st, 0.0, (double)g.cells * (8.0 + n_views * per_view));
-    hipLaunchKernelGGL(k_rectify, dim3(blocks_of(g.cells)), dim3(kRectifyThreads), 0, st, g, dsm, cameras, images, pix, rgb, valid);
+    hipLaunchKernelGGL(k_rectify, dim3(blocks_of(g.cells, kRectifyThreads)), dim3(kRectifyThreads), 0, st, g, dsm, cameras, images, pix, rgb, valid);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -238,7 +236,7 @@ extern "C" int32_t spnerf_rectify_sample(const spnerf_rectify_image* images, int
     SPN_TRY(check_views("rectify_sample", n_views));
     SPN_TRY(check_channels("rectify_sample", channels));
     ProfScope prof("rectify_sample", st, 0.0, (double)cells * n_views * (16.0 + 20.0 * channels + 1.0));
-    hipLaunchKernelGGL(k_rectify_sample, dim3(blocks_of(cells)), dim3(kRectifyThreads), 0, st, images, n_views, channels, pix, cells, rgb,
+    hipLaunchKernelGGL(k_rectify_sample, dim3(blocks_of(cells, kRectifyThreads)), dim3(kRectifyThreads), 0, st, images, n_views, channels, pix, cells, rgb,
                        valid);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
@@ -278,7 +276,7 @@ extern "C" int32_t spnerf_rectify_mosaic(const float* rgb, const uint8_t* usable
     SPN_ARG(mode == SPNERF_RECTIFY_MEAN || mode == SPNERF_RECTIFY_MEDIAN, "rectify_mosaic: mode %d is neither 0 (mean) nor 1 (median)",
             mode);
     ProfScope prof("rectify_mosaic", st, 0.0, (double)cells * (n_views * (4.0 * channels + 1.0) + 4.0 * channels + 8.0));
-    hipLaunchKernelGGL(k_rectify_mosaic, dim3(blocks_of(cells)), dim3(kRectifyThreads), 0, st, rgb, usable, n_views, cells, channels, mode,
+    hipLaunchKernelGGL(k_rectify_mosaic, dim3(blocks_of(cells, kRectifyThreads)), dim3(kRectifyThreads), 0, st, rgb, usable, n_views, cells, channels, mode,
                        mosaic, count, spread);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;

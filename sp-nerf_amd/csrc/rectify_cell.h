@@ -1,10 +1,11 @@
 // One cell of the ground grid in one camera, shared by the orthorectification (rectify.hip) and the
-// plane sweep (sweep.hip): the RPC projection on a packed camera and the bilinear read, as
+// plane sweep (sweep.hip): the RPC projection on a packed camera, its inverse (dsm_view.hip) and the bilinear read, as
 // include/spnerf_amd_rectify.h states them, and the host check of a grid.
 #pragma once
 #include <cmath>
 
 #include "../../include/spnerf_amd_rectify.h"
+#include "ground.h"
 #include "rpc.h"
 
 namespace spn {
@@ -17,6 +18,20 @@ __device__ __forceinline__ void project_packed(const double* __restrict__ c, dou
     const double la = (lat - c[2]) / c[7], lo = (lon - c[3]) / c[8], al = (alt - c[4]) / c[9];
     col = rpoly(c + 50, la, lo, al) / rpoly(c + 70, la, lo, al) * c[6] + c[1];
     row = rpoly(c + 10, la, lo, al) / rpoly(c + 30, la, lo, al) * c[5] + c[0];
+}
+
+// The iteration of csrc/rpc.h (localize_n, the one spnerf_rpc_rays runs) over the projection of a packed camera
+// c: normalised image (cn, rn) at the normalised altitude an -> degrees (lat, lon).
+__device__ __forceinline__ void proj_packed_n(const double* __restrict__ c, double lat, double lon, double an, double& x, double& y) {
+    x = rpoly(c + 50, lat, lon, an) / rpoly(c + 70, lat, lon, an);
+    y = rpoly(c + 10, lat, lon, an) / rpoly(c + 30, lat, lon, an);
+}
+
+__device__ __forceinline__ void localize_packed(const double* __restrict__ c, double cn, double rn, double an, double& lat_d, double& lon_d) {
+    double lon, lat;
+    localize_n([c](double la, double lo, double al, double& x, double& y) { proj_packed_n(c, la, lo, al, x, y); }, cn, rn, an, lon, lat);
+    lon_d = lon * c[8] + c[3];
+    lat_d = lat * c[7] + c[2];
 }
 
 // the bilinear read of include/spnerf_amd_rectify.h; false (and NaN in every channel) outside the image
@@ -45,9 +60,7 @@ __device__ __forceinline__ bool sample_cell(const spnerf_rectify_image im, int C
 }
 
 inline int32_t check_grid(const char* who, const spnerf_ortho_grid* g) {
-    SPN_ARG(g->xsize > 0 && g->ysize > 0, "%s: grid of %d x %d cells", who, g->xsize, g->ysize);
-    SPN_ARG((int64_t)g->xsize * g->ysize <= ((int64_t)1 << 32), "%s: grid of %d x %d cells is too large for one call", who, g->xsize,
-            g->ysize);
+    SPN_TRY(check_cells(who, g->ysize, g->xsize));
     SPN_ARG(g->zone >= 1 && g->zone <= 60, "%s: UTM zone %d", who, g->zone);
     SPN_ARG(g->resolution > 0.0 && std::isfinite(g->resolution), "%s: resolution %g", who, g->resolution);
     SPN_ARG(std::isfinite(g->xoff) && std::isfinite(g->ytop), "%s: non-finite grid origin", who);

@@ -50,7 +50,7 @@ __device__ __forceinline__ void proj_n(const RpcCam& a, double lat, double lon, 
 
 // The iteration itself, over any projection proj(lat, lon, an, col, row) on normalised coordinates: normalised
 // image (cn, rn) at normalised altitude an → normalised (lon, lat).  Stated once: localize below runs it on an
-// RpcCam, csrc/dsm_view.hip on a packed camera table.
+// RpcCam, localize_packed (csrc/rectify_cell.h) on a packed camera table.
 template <class Proj>
 __device__ __forceinline__ void localize_n(Proj proj, double cn, double rn, double an, double& lon_n, double& lat_n) {
     double lon = -1.0, lat = -1.0, eps = 2.0;

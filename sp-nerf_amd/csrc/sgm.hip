@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "ground.h"
 
 #pragma clang fp contract(off)
 
@@ -210,8 +211,7 @@ __global__ __launch_bounds__(kSgmThreads) void k_sgm_pick(const float* __restric
 
 static int32_t check_sizes(const char* who, int32_t n_planes, int32_t ysize, int32_t xsize, int32_t paths) {
     SPN_ARG(n_planes >= 1 && n_planes <= SPNERF_SGM_MAX_PLANES, "%s: n_planes %d outside [1, %d]", who, n_planes, SPNERF_SGM_MAX_PLANES);
-    SPN_ARG(xsize > 0 && ysize > 0, "%s: grid of %d x %d cells", who, xsize, ysize);
-    SPN_ARG((int64_t)xsize * ysize <= ((int64_t)1 << 32), "%s: grid of %d x %d cells is too large for one call", who, xsize, ysize);
+    SPN_TRY(check_cells(who, ysize, xsize));
     SPN_ARG(paths == 4 || paths == 8, "%s: paths %d must be 4 or 8", who, paths);
     return SPNERF_OK;
 }

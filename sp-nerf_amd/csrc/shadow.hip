@@ -19,6 +19,7 @@
 #include "../../include/spnerf_amd_shadow.h"
 #include "common.h"
 #include "shadow_march.h"
+#include "wave.h"
 
 namespace spn {
 
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(kShadowThreads) void k_shadow_hmax(const double* __
         const double x = dsm[c];
         if (x == x) v = fmax(v, x);
     }
-    v = wave_max_f64(v);
+    v = wave_max(v);
     if ((tid & 63) == 0) s_max[tid >> 6] = v;
     __syncthreads();
     if (tid == 0) {
@@ -91,17 +92,6 @@ static int agree_blocks(int64_t cells) {
     return (int)(nb < kAgreeMaxBlocks ? nb : kAgreeMaxBlocks);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off, 64);
-    return v;
-}
-
 // part[(k·nb + b)] is workgroup b's share of direction k
 __global__ __launch_bounds__(kAgreeThreads) void k_shadow_agreement(const float* __restrict__ sun,
                                                                     const uint8_t* __restrict__ shadow, int64_t cells,
@@ -127,9 +117,9 @@ __global__ __launch_bounds__(kAgreeThreads) void k_shadow_agreement(const float*
         n[4] += (s == 1 && !dark);
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) f[a] = wave_sum_f64(f[a]);
+    for (int a = 0; a < 3; ++a) f[a] = wave_sum(f[a]);
 #pragma unroll
-    for (int a = 0; a < 5; ++a) n[a] = wave_sum_i64(n[a]);
+    for (int a = 0; a < 5; ++a) n[a] = wave_sum(n[a]);
     if ((tid & 63) == 0) {
         for (int a = 0; a < 3; ++a) s_f[tid >> 6][a] = f[a];
         for (int a = 0; a < 5; ++a) s_n[tid >> 6][a] = n[a];
@@ -160,8 +150,6 @@ __global__ __launch_bounds__(kAgreeThreads) void k_shadow_agreement_finish(const
         res[k] = t;
     }
 }
-
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 static int32_t check_grid(const char* who, int32_t height, int32_t width) {
     SPN_ARG(height > 0 && width > 0, "%s: grid of %d x %d cells", who, width, height);

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "wave.h"
 
 namespace spn {
 
@@ -16,12 +17,6 @@ constexpr int kShadowMaxParts = 256;      // partial maxima: 2 KiB, reduced by t
 // the partial maxima of the non-NaN heights, one launch into `part` (shadow.hip); hmax_parts entries
 int hmax_parts(int64_t cells);
 void launch_shadow_hmax(const double* dsm, int64_t cells, double* part, hipStream_t st);
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // One direction's march, prepared on the host: axis 0 steps along the columns, 1 along the rows,
 // -1 takes no step (a = b = 0); sgn is the step's sign along that axis.
@@ -52,7 +47,7 @@ __device__ __forceinline__ double block_hmax(const double* __restrict__ part, in
     if (tid < 64) {
         double v = -INFINITY;
         for (int p = tid; p < nparts; p += 64) v = fmax(v, part[p]);
-        v = wave_max_f64(v);
+        v = wave_max(v);
         if (tid == 0) *s_hmax = v;
     }
     __syncthreads();

@@ -84,8 +84,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_surface_upsample(const float*
     out[cell] = den > 0.0 ? (float)(num / den) : NAN;
 }
 
-static unsigned blocks_of(int64_t n) { return (unsigned)((n + kSweepThreads - 1) / kSweepThreads); }
-
 }  // namespace spn
 
 using namespace spn;
@@ -106,7 +104,7 @@ extern "C" int32_t spnerf_surface_grey(const spnerf_ortho_grid* grid, const doub
     const int64_t cells = (int64_t)g.xsize * g.ysize;
     ProfScope prof("surface_grey", st, (double)cells * n_views * grey_flop(channels),
                    (double)cells * (4.0 + n_views * (16.0 * channels + 5.0)));
-    hipLaunchKernelGGL(k_surface_grey, dim3(blocks_of(cells)), dim3(kSweepThreads), 0, st, g, offset, cameras, images, base, grey, valid);
+    hipLaunchKernelGGL(k_surface_grey, dim3(blocks_of(cells, kSweepThreads)), dim3(kSweepThreads), 0, st, g, offset, cameras, images, base, grey, valid);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -116,7 +114,7 @@ extern "C" int32_t spnerf_surface_lift(const float* base, const float* rel, int6
     SPN_ARG(base && rel && out, "surface_lift: NULL base, rel or out");
     SPN_ARG(count >= 1 && count <= ((int64_t)1 << 32), "surface_lift: count %lld outside [1, 2^32]", (long long)count);
     ProfScope prof("surface_lift", st, (double)count, (double)count * 12.0);
-    hipLaunchKernelGGL(k_surface_lift, dim3(blocks_of(count)), dim3(kSweepThreads), 0, st, base, rel, count, out);
+    hipLaunchKernelGGL(k_surface_lift, dim3(blocks_of(count, kSweepThreads)), dim3(kSweepThreads), 0, st, base, rel, count, out);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -126,12 +124,11 @@ extern "C" int32_t spnerf_surface_upsample(const float* coarse, int32_t factor, 
     SPN_ARG(coarse && out, "surface_upsample: NULL coarse or out");
     SPN_ARG(factor >= 1 && factor <= SPNERF_SURFACE_MAX_FACTOR, "surface_upsample: factor %d outside [1, %d]", factor,
             SPNERF_SURFACE_MAX_FACTOR);
-    SPN_ARG(xsize > 0 && ysize > 0, "surface_upsample: grid of %d x %d cells", xsize, ysize);
-    SPN_ARG((int64_t)xsize * ysize <= ((int64_t)1 << 32), "surface_upsample: grid of %d x %d cells is too large for one call", xsize, ysize);
+    SPN_TRY(check_cells("surface_upsample", ysize, xsize));
     const int hc = (int)(((int64_t)ysize + factor - 1) / factor), wc = (int)(((int64_t)xsize + factor - 1) / factor);
     const int64_t cells = (int64_t)xsize * ysize;
     ProfScope prof("surface_upsample", st, (double)cells * 16.0, (double)cells * 4.0 + (double)hc * wc * 4.0);
-    hipLaunchKernelGGL(k_surface_upsample, dim3(blocks_of(cells)), dim3(kSweepThreads), 0, st, coarse, factor, hc, wc, ysize, xsize, out);
+    hipLaunchKernelGGL(k_surface_upsample, dim3(blocks_of(cells, kSweepThreads)), dim3(kSweepThreads), 0, st, coarse, factor, hc, wc, ysize, xsize, out);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }

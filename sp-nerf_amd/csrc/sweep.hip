@@ -66,8 +66,6 @@ __global__ __launch_bounds__(kSweepThreads) void k_sweep_pick(const float* __res
     views[cell] = (uint8_t)p.m;
 }
 
-static unsigned blocks_of(int64_t cells) { return (unsigned)((cells + kSweepThreads - 1) / kSweepThreads); }
-
 }  // namespace spn
 
 using namespace spn;
@@ -86,7 +84,7 @@ extern "C" int32_t spnerf_sweep_grey(const spnerf_ortho_grid* grid, const double
     g.xsize = grid->xsize; g.ysize = grid->ysize; g.zone = grid->zone; g.south = grid->south ? 1 : 0; g.V = n_views; g.C = channels;
     const int64_t cells = (int64_t)g.xsize * g.ysize;
     ProfScope prof("sweep_grey", st, (double)cells * n_views * grey_flop(channels), (double)cells * n_views * (16.0 * channels + 5.0));
-    hipLaunchKernelGGL(k_sweep_grey, dim3(blocks_of(cells)), dim3(kSweepThreads), 0, st, g, alt, cameras, images, grey, valid);
+    hipLaunchKernelGGL(k_sweep_grey, dim3(blocks_of(cells, kSweepThreads)), dim3(kSweepThreads), 0, st, g, alt, cameras, images, grey, valid);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;
 }
@@ -95,8 +93,7 @@ extern "C" int32_t spnerf_sweep_score(const float* grey, const uint8_t* valid, i
                                       int32_t radius, int32_t min_views, double min_std, float* score, uint8_t* views, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     SPN_ARG(grey && valid && score && views, "sweep_score: NULL grey, valid, score or views");
-    SPN_ARG(xsize > 0 && ysize > 0, "sweep_score: grid of %d x %d cells", xsize, ysize);
-    SPN_ARG((int64_t)xsize * ysize <= ((int64_t)1 << 32), "sweep_score: grid of %d x %d cells is too large for one call", xsize, ysize);
+    SPN_TRY(check_cells("sweep_score", ysize, xsize));
     SPN_TRY(check_views_channels("sweep_score", n_views, 1));
     SPN_TRY(check_window("sweep_score", n_views, radius, min_views, min_std));
     int tx;
@@ -124,7 +121,7 @@ extern "C" int32_t spnerf_sweep_pick(const float* volume, const uint8_t* views_v
     SPN_ARG(cells >= 1 && cells <= ((int64_t)1 << 32), "sweep_pick: cells %lld outside [1, 2^32]", (long long)cells);
     SPN_TRY(check_planes("sweep_pick", n_planes, alt_lo, step));
     ProfScope prof("sweep_pick", st, 0.0, (double)cells * (n_planes * 5.0 + 13.0));
-    hipLaunchKernelGGL(k_sweep_pick, dim3(blocks_of(cells)), dim3(kSweepThreads), 0, st, volume, views_vol, n_planes, cells, alt_lo, step,
+    hipLaunchKernelGGL(k_sweep_pick, dim3(blocks_of(cells, kSweepThreads)), dim3(kSweepThreads), 0, st, volume, views_vol, n_planes, cells, alt_lo, step,
                        altitude, score, index, views);
     SPN_HIP(hipGetLastError());
     return SPNERF_OK;

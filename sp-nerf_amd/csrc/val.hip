@@ -94,12 +94,6 @@ struct LossArgs {
     double* part;   // [blocks][kLossSums]
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kLossThreads) void k_val_loss(LossArgs m) {
     __shared__ double s_part[kLossThreads / 64][kLossSums];
     const int tid = threadIdx.x;
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(kLossThreads) void k_val_loss(LossArgs m) {
     }
 #pragma unroll
     for (int k = 0; k < kLossSums; ++k) {
-        const double t = wave_sum_f64(acc[k]);
+        const double t = wave_sum(acc[k]);
         if ((tid & 63) == 0) s_part[tid >> 6][k] = t;
     }
     __syncthreads();

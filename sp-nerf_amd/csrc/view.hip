@@ -171,12 +171,6 @@ struct MetricArgs {
     int64_t* tab;   // [blocks][(C + 1) * C]
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(kMetricThreads) void k_view_metrics(MetricArgs m) {
     __shared__ unsigned int s_tab[kTableMax];
     __shared__ double s_sq[kMetricThreads / 64];
@@ -221,7 +215,7 @@ __global__ __launch_bounds__(kMetricThreads) void k_view_metrics(MetricArgs m) {
             if (c >= 0 && c < m.C) atomicAdd(&s_tab[row * m.C + c], 1u);
         }
     }
-    acc = wave_sum_f64(acc);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) s_sq[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -256,8 +250,6 @@ __global__ __launch_bounds__(kMetricThreads) void k_view_metrics_finish(MetricAr
         res->correct = ok;
     }
 }
-
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 }  // namespace spn
 

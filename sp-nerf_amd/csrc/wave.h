@@ -10,6 +10,31 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// the same butterfly over the other types that are reduced: offsets 32 down to 1, so every lane ends with
+// the same sum, in the same order, whichever overload it came through
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ int64_t wave_sum(int64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (int64_t)__shfl_xor((long long)v, off, 64);
+    return v;
+}
+
+// the maximum over the 64 lanes, in every lane (fmaxf / fmax: a NaN lane loses to a number)
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // the minimum over the 64 lanes, in every lane (exact, so the butterfly's order does not matter; no NaN expected)
 __device__ __forceinline__ float wave_fmin(float v) {
 #pragma unroll

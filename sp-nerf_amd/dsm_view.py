@@ -27,21 +27,14 @@ import torch
 
 from . import _dsmview_lib, _lib
 from .ortho import GroundGrid
-from .rectify import Camera, _camera_table, _check_alts, _check_grid, _grid_struct
-from .sweep import _check_int, _check_real, _one_device, _what
+from ._ground import _camera_table, _check_alts, _check_grid, _check_int, _check_raster, _check_real, _grid_struct, _one_device, _what
+from .rectify import Camera
 
 MODES = {"nearest": _dsmview_lib.DSMVIEW_NEAREST, "bilinear": _dsmview_lib.DSMVIEW_BILINEAR}
 INT32_MAX = 2 ** 31 - 1
 
 
 # ---- argument checks: everything below is decided on the host, before any device is touched ------
-
-def _check_raster(name, t, shape=None):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.numel() == 0 or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a non-empty (H, W) float32 tensor, got {_what(t)}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} {tuple(t.shape)} is not the grid's {tuple(shape)}")
-
 
 def _check_camera(camera):
     if not isinstance(camera, Camera):

@@ -25,9 +25,8 @@ import torch
 
 from . import _lib, _occlusion_lib, sgm
 from . import sweep as _sweep
-from .rectify import _camera_table, _grid_struct, _image_table, view_directions
-from .shadow import _resolution
-from .sweep import _check_real, _one_device, _what
+from ._ground import _camera_table, _check_dsm, _check_int, _check_real, _grid_struct, _image_table, _one_device, _pick_planes, _resolution, _what
+from .rectify import view_directions
 
 MAX_VIEWS = _occlusion_lib.OCCLUSION_MAX_VIEWS
 
@@ -36,11 +35,6 @@ MAX_VIEWS = _occlusion_lib.OCCLUSION_MAX_VIEWS
 
 def _check_slack(slack):
     return _check_real("slack", slack, "finite and >= 0", lambda x: x >= 0)
-
-
-def _check_dsm(name, dsm):
-    if not isinstance(dsm, torch.Tensor) or dsm.dim() != 2 or dsm.numel() == 0 or dsm.dtype not in (torch.float32, torch.float64):
-        raise ValueError(f"{name} must be a non-empty (H, W) float64 or float32 tensor, got {_what(dsm)}")
 
 
 def _check_floor(floor, shape):
@@ -132,10 +126,7 @@ def visible_sweep(images, cameras, grid, alt_lo, step, planes, floor, *, slack, 
     cam_table = _camera_table(cams, dev)
     img_table, imgs = _image_table(imgs, dev)
     floor = floor.contiguous()
-    out = {"altitude": torch.empty((H, W), dtype=torch.float32, device=dev), "score": torch.empty((H, W), dtype=torch.float32, device=dev),
-           "index": torch.empty((H, W), dtype=torch.int32, device=dev), "views": torch.empty((H, W), dtype=torch.uint8, device=dev)}
-    if volume:
-        out["volume"] = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    out = _pick_planes(H, W, dev, K if volume else None)
     _lib.check(L.spnerf_occlusion_sweep(ctypes.byref(_grid_struct(grid)), _lib.ptr(cam_table), _lib.ptr(img_table), V, C, alt_lo, step, K,
                                         radius, min_views, min_std, _lib.ptr(floor), slack, _lib.ptr(out["altitude"]),
                                         _lib.ptr(out["score"]), _lib.ptr(out["index"]), _lib.ptr(out["views"]), _lib.ptr(out.get("volume")),
@@ -157,16 +148,14 @@ def refine_sweep(images, cameras, grid, alt_lo, step, planes, *, prior=None, sla
     first pass makes it worse."""
     cams, imgs, grid = _sweep._check_scene(images, cameras, grid)
     alt_lo, step, K = _sweep._check_planes(alt_lo, step, planes)
-    _sweep._check_int("planes", K, 2, sgm.MAX_PLANES)
+    _check_int("planes", K, 2, sgm.MAX_PLANES)
     _sweep._check_window(len(cams), radius, min_views, min_std)
     sgm._check_penalties(p1, p2, unscored, paths)
     slack = step if slack is None else _check_slack(slack)
     if not isinstance(volume, bool):
         raise ValueError(f"volume {volume!r} must be a bool")
     if prior is not None:
-        _check_dsm("prior", prior)
-        if tuple(prior.shape) != grid.shape:
-            raise ValueError(f"prior {tuple(prior.shape)} is not the grid's {grid.shape}")
+        _check_dsm("prior", prior, grid)
         _one_device(*imgs, prior)
     kw = dict(radius=radius, min_views=min_views, min_std=min_std)
     if prior is None:

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, _ortho_lib
+from ._ground import _require_cuda
 from .relight import PRODUCTS as RELIGHT_PRODUCTS, SUN_PLANES, _directions, relight_image
 from .satellite import sun_direction
 from .view import PRODUCTS as VIEW_PRODUCTS, render_image
@@ -153,13 +154,6 @@ def _check_semantics(semantics, grid):
     if shape != grid.shape:
         raise ValueError(f"semantics must hold one label per cell, {grid.shape}, got {shape}")
     return semantics
-
-
-def _require_cuda(device):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.SpnerfError(f"spnerf_amd runs the render path on the MI355X (HIP) only; got device {dev}.")
-    return dev
 
 
 def _launch_rays(grid, s, j0, j1, min_alt, max_alt, cen, rng, sun, dev):

@@ -25,8 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib, _rectify_lib
-from ._ortho_lib import OrthoGrid
-from .ortho import GroundGrid, _require_cuda
+from ._ground import (_camera_table, _check_alts, _check_cameras, _check_dsm, _check_grid, _check_images, _grid_struct, _image_table,
+                      _require_cuda, _require_one_device, _what)
+from .ortho import GroundGrid
 from .satellite import RPCModel, rescale_rpc
 
 MAX_VIEWS = _rectify_lib.RECTIFY_MAX_VIEWS
@@ -67,86 +68,10 @@ class Camera:
 
 # ---- argument checks: everything below is decided on the host, before any device is touched ------
 
-def _check_cameras(cameras):
-    cams = [cameras] if isinstance(cameras, Camera) else list(cameras)
-    if not cams or len(cams) > MAX_VIEWS:
-        raise ValueError(f"{len(cams)} cameras in one call (1 to {MAX_VIEWS})")
-    for v, c in enumerate(cams):
-        if not isinstance(c, Camera):
-            raise ValueError(f"cameras[{v}] must be a rectify.Camera, got {type(c).__name__}")
-    return cams
-
-
-def _check_grid(grid):
-    if not isinstance(grid, GroundGrid):
-        raise ValueError(f"grid must be a GroundGrid, got {type(grid).__name__}")
-    return grid
-
-
-def _check_dsm(dsm, grid):
-    if not isinstance(dsm, torch.Tensor) or dsm.dim() != 2 or dsm.numel() == 0 or dsm.dtype not in (torch.float32, torch.float64):
-        what = f"{dsm.dtype} {tuple(dsm.shape)}" if isinstance(dsm, torch.Tensor) else type(dsm).__name__
-        raise ValueError(f"dsm must be a non-empty (H, W) float64 or float32 tensor, got {what}")
-    if tuple(dsm.shape) != _check_grid(grid).shape:
-        raise ValueError(f"dsm {tuple(dsm.shape)} is not the grid's {grid.shape}")
-
-
-def _check_images(images, n_views=None, cameras=None):
-    imgs = list(images) if isinstance(images, (list, tuple, torch.Tensor)) else None
-    if not imgs or len(imgs) > MAX_VIEWS:
-        raise ValueError(f"images must be 1 to {MAX_VIEWS} (h, w, C) tensors, got {type(images).__name__ if imgs is None else len(imgs)}")
-    for v, im in enumerate(imgs):
-        if (not isinstance(im, torch.Tensor) or im.dim() != 3 or im.numel() == 0 or im.dtype != torch.float32
-                or im.shape[2] > MAX_CHANNELS):
-            what = f"{im.dtype} {tuple(im.shape)}" if isinstance(im, torch.Tensor) else type(im).__name__
-            raise ValueError(f"images[{v}] must be a non-empty (h, w, C) float32 tensor with C <= {MAX_CHANNELS}, got {what}")
-        if im.shape[2] != imgs[0].shape[2]:
-            raise ValueError(f"images[{v}] has {im.shape[2]} channels, images[0] has {imgs[0].shape[2]}")
-    if n_views is not None and len(imgs) != n_views:
-        raise ValueError(f"{len(imgs)} images for {n_views} views")
-    if cameras is not None:
-        for v, (im, cam) in enumerate(zip(imgs, cameras)):
-            if cam.shape is not None and tuple(im.shape[:2]) != cam.shape:
-                raise ValueError(f"images[{v}] is {tuple(im.shape[:2])}, its camera's image is {cam.shape}")
-    return imgs
-
-
-def _check_alts(alt_lo, alt_hi):
-    alt_lo, alt_hi = float(alt_lo), float(alt_hi)
-    if not (math.isfinite(alt_lo) and math.isfinite(alt_hi) and alt_hi > alt_lo):
-        raise ValueError(f"alt_hi {alt_hi} must be above alt_lo {alt_lo}")
-    return alt_lo, alt_hi
-
-
 def _check_mode(mode):
     if mode not in MODES:
         raise ValueError(f"mosaic mode {mode!r} is neither 'mean' nor 'median'")
     return MODES[mode]
-
-
-# ---- the tables the kernels read, in device memory -------------------------------------------------
-
-def _grid_struct(grid):
-    return OrthoGrid(grid.xoff, grid.ytop, grid.resolution, grid.xsize, grid.ysize, grid.zone, 1 if grid.south else 0, 1)
-
-
-def _camera_table(cams, device):
-    return torch.from_numpy(np.stack([c.packed() for c in cams])).to(device)
-
-
-def _image_table(imgs, device):
-    """(table, images): the device table of spnerf_rectify_image and the contiguous images it points to."""
-    imgs = [im.contiguous() for im in imgs]
-    rows = (_rectify_lib.RectifyImage * len(imgs))(*[_rectify_lib.RectifyImage(im.data_ptr(), im.shape[0], im.shape[1]) for im in imgs])
-    table = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8).to(device)
-    return table, imgs
-
-
-def _require_one_device(*tensors):
-    _lib.require_device(*tensors)
-    if len({t.device for t in tensors}) != 1:
-        raise _lib.SpnerfError(f"the tensors of one call must be on one device, got {sorted({str(t.device) for t in tensors})}")
-    return tensors[0].device
 
 
 # ---- the steps ----------------------------------------------------------------------------------------
@@ -156,7 +81,7 @@ def project_cells(dsm: torch.Tensor, grid: GroundGrid, cameras) -> torch.Tensor:
     altitude ``dsm`` (H, W) in each of ``cameras``; NaN where the DSM is NaN.  The inverse projection of
     a cell is computed once for all views."""
     cams = _check_cameras(cameras)
-    _check_dsm(dsm, grid)
+    _check_dsm("dsm", dsm, grid)
     dev = _require_one_device(dsm)
     L = _rectify_lib.lib()
     dsm = dsm.double().contiguous()
@@ -175,8 +100,7 @@ def sample_images(images, pix: torch.Tensor):
     order), cast once.  An invalid cell is NaN in every channel."""
     imgs = _check_images(images)
     if not isinstance(pix, torch.Tensor) or pix.dim() != 4 or pix.shape[3] != 2 or pix.numel() == 0 or pix.dtype != torch.float64:
-        what = f"{pix.dtype} {tuple(pix.shape)}" if isinstance(pix, torch.Tensor) else type(pix).__name__
-        raise ValueError(f"pix must be a non-empty (V, H, W, 2) float64 tensor, got {what}")
+        raise ValueError(f"pix must be a non-empty (V, H, W, 2) float64 tensor, got {_what(pix)}")
     if pix.shape[0] != len(imgs):
         raise ValueError(f"{len(imgs)} images for {pix.shape[0]} views")
     dev = _require_one_device(pix, *imgs)
@@ -221,11 +145,9 @@ def mosaic(rgb: torch.Tensor, usable: torch.Tensor, mode: str = "median"):
     A cell no view can use is NaN in both float planes."""
     if (not isinstance(rgb, torch.Tensor) or rgb.dim() != 4 or rgb.numel() == 0 or rgb.dtype != torch.float32
             or rgb.shape[0] > MAX_VIEWS or rgb.shape[3] > MAX_CHANNELS):
-        what = f"{rgb.dtype} {tuple(rgb.shape)}" if isinstance(rgb, torch.Tensor) else type(rgb).__name__
-        raise ValueError(f"rgb must be a non-empty (V, H, W, C) float32 tensor with V <= {MAX_VIEWS} and C <= {MAX_CHANNELS}, got {what}")
+        raise ValueError(f"rgb must be a non-empty (V, H, W, C) float32 tensor with V <= {MAX_VIEWS} and C <= {MAX_CHANNELS}, got {_what(rgb)}")
     if not isinstance(usable, torch.Tensor) or usable.dtype != torch.uint8 or tuple(usable.shape) != tuple(rgb.shape[:3]):
-        what = f"{usable.dtype} {tuple(usable.shape)}" if isinstance(usable, torch.Tensor) else type(usable).__name__
-        raise ValueError(f"usable must be a {tuple(rgb.shape[:3])} uint8 tensor, got {what}")
+        raise ValueError(f"usable must be a {tuple(rgb.shape[:3])} uint8 tensor, got {_what(usable)}")
     code = _check_mode(mode)
     dev = _require_one_device(rgb, usable)
     L = _rectify_lib.lib()
@@ -262,7 +184,7 @@ def orthorectify(images, cameras, dsm: torch.Tensor, grid: GroundGrid, alt_lo, a
     that does not see the grid) raises ``cast_shadows``' ``ValueError`` only then."""
     cams = _check_cameras(cameras)
     imgs = _check_images(images, len(cams), cams)
-    _check_dsm(dsm, grid)
+    _check_dsm("dsm", dsm, grid)
     alt_lo, alt_hi = _check_alts(alt_lo, alt_hi)
     code = None if mosaic is None else _check_mode(mosaic)
     dev = _require_one_device(dsm, *imgs)

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib, _sgm_lib
 from . import sweep as _sweep
-from .sweep import _check_int, _check_real, _one_device, _what
+from ._ground import _check_int, _check_real, _one_device, _what
 
 MAX_PLANES = _sgm_lib.SGM_MAX_PLANES
 # the defaults, chosen on the 512 x 512 JAX_269 ROI, 64 planes half a metre apart, radius 2 (profiles/r22/sgm.txt,

@@ -10,13 +10,12 @@ result: EO-NeRF's consistency of the learnt shadows with the learnt geometry, as
 from __future__ import annotations
 
 import ctypes
-import math
-import numbers
 
 import numpy as np
 import torch
 
 from . import _lib, _shadow_lib
+from ._ground import _check_dsm, _resolution
 from .relight import _directions
 from .satellite import sun_direction
 
@@ -46,20 +45,6 @@ def sun_directions(sun_dirs) -> torch.Tensor:
     return dirs
 
 
-def _resolution(resolution_or_grid, shape):
-    from .ortho import GroundGrid
-    if isinstance(resolution_or_grid, GroundGrid):
-        if tuple(shape) != resolution_or_grid.shape:
-            raise ValueError(f"dsm {tuple(shape)} is not the grid's {resolution_or_grid.shape}")
-        return resolution_or_grid.resolution
-    if not isinstance(resolution_or_grid, numbers.Real) or isinstance(resolution_or_grid, bool):
-        raise ValueError(f"resolution_or_grid must be a GroundGrid or the cell size in metres, got {resolution_or_grid!r}")
-    res = float(resolution_or_grid)
-    if not (math.isfinite(res) and res > 0):
-        raise ValueError(f"resolution {res} must be positive")
-    return res
-
-
 def cast_shadows(dsm: torch.Tensor, resolution_or_grid, sun_dirs, excess: bool = False):
     """Cast the (H, W) device DSM ``dsm`` — float64, or float32 (widened) — row 0 the northernmost (the
     ``GroundGrid`` layout; ``render_ortho``'s "dsm"), cells of ``resolution_or_grid`` metres, under the K
@@ -73,9 +58,7 @@ def cast_shadows(dsm: torch.Tensor, resolution_or_grid, sun_dirs, excess: bool =
     The march of a cell follows the grid along the major axis of the sun's azimuth, one column (or
     row) per step, interpolating the heights linearly across the other axis; NaN heights on the way
     are skipped.  Arithmetic is fp64; the result is bit-reproducible (include/spnerf_amd_shadow.h)."""
-    if not isinstance(dsm, torch.Tensor) or dsm.dim() != 2 or dsm.numel() == 0 or dsm.dtype not in (torch.float32, torch.float64):
-        what = f"{dsm.dtype} {tuple(dsm.shape)}" if isinstance(dsm, torch.Tensor) else type(dsm).__name__
-        raise ValueError(f"dsm must be a non-empty (H, W) float64 or float32 tensor, got {what}")
+    _check_dsm("dsm", dsm)
     res = _resolution(resolution_or_grid, dsm.shape)
     dirs = sun_directions(sun_dirs)
     K, (H, W) = dirs.shape[0], dsm.shape

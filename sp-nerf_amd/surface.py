@@ -27,20 +27,13 @@ import torch
 from . import _lib, _surface_lib, sgm
 from . import sweep as _sweep
 from .ortho import GroundGrid
-from .rectify import _camera_table, _check_grid, _grid_struct, _image_table
-from .sweep import _check_int, _check_real, _one_device, _what
+from ._ground import (_camera_table, _check_grid, _check_int, _check_raster, _check_real, _grid_struct, _image_table, _one_device,
+                      _pick_planes)
 
 MAX_FACTOR = _surface_lib.SURFACE_MAX_FACTOR
 
 
 # ---- argument checks: everything below is decided on the host, before any device is touched ------
-
-def _check_raster(name, t, shape=None):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.numel() == 0 or t.dtype != torch.float32:
-        raise ValueError(f"{name} must be a non-empty (H, W) float32 tensor, got {_what(t)}")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} {tuple(t.shape)} is not the grid's {tuple(shape)}")
-
 
 def _check_shape(shape):
     try:
@@ -172,10 +165,7 @@ def surface_sweep(images, cameras, grid, base: torch.Tensor, off_lo, step, plane
     cam_table = _camera_table(cams, dev)
     img_table, imgs = _image_table(imgs, dev)
     base = base.contiguous()
-    out = {"altitude": torch.empty((H, W), dtype=torch.float32, device=dev), "score": torch.empty((H, W), dtype=torch.float32, device=dev),
-           "index": torch.empty((H, W), dtype=torch.int32, device=dev), "views": torch.empty((H, W), dtype=torch.uint8, device=dev)}
-    if volume:
-        out["volume"] = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    out = _pick_planes(H, W, dev, K if volume else None)
     _lib.check(L.spnerf_surface_sweep(ctypes.byref(_grid_struct(grid)), _lib.ptr(cam_table), _lib.ptr(img_table), V, C, _lib.ptr(base),
                                       off_lo, step, K, radius, min_views, min_std, _lib.ptr(out["altitude"]), _lib.ptr(out["score"]),
                                       _lib.ptr(out["index"]), _lib.ptr(out["views"]), _lib.ptr(out.get("volume")),

@@ -16,13 +16,12 @@ Conventions are ``rectify``'s: cameras are ``rectify.Camera``s, an image is a de
 from __future__ import annotations
 
 import ctypes
-import math
-import numbers
 
 import torch
 
 from . import _lib, _sweep_lib
-from .rectify import _camera_table, _check_cameras, _check_grid, _check_images, _grid_struct, _image_table
+from ._ground import (_camera_table, _check_cameras, _check_grid, _check_images, _check_int, _check_real, _grid_struct, _image_table,
+                      _one_device, _pick_planes, _what)
 
 MIN_VIEWS = _sweep_lib.SWEEP_MIN_VIEWS
 MAX_VIEWS = _sweep_lib.SWEEP_MAX_VIEWS
@@ -35,18 +34,6 @@ MAX_RADIUS = _sweep_lib.SWEEP_MAX_RADIUS
 def _check_view_count(n):
     if not MIN_VIEWS <= n <= MAX_VIEWS:
         raise ValueError(f"{n} views in one sweep ({MIN_VIEWS} to {MAX_VIEWS})")
-
-
-def _check_int(name, value, lo, hi):
-    if not isinstance(value, numbers.Integral) or isinstance(value, bool) or not lo <= value <= hi:
-        raise ValueError(f"{name} {value!r} must be an integer in {lo}..{hi}")
-    return int(value)
-
-
-def _check_real(name, value, what, ok):
-    if not isinstance(value, numbers.Real) or isinstance(value, bool) or not math.isfinite(value) or not ok(value):
-        raise ValueError(f"{name} {value!r} must be {what}")
-    return float(value)
 
 
 def _check_planes(alt_lo, step, planes):
@@ -64,18 +51,6 @@ def _check_scene(images, cameras, grid):
     _check_view_count(len(cams))
     imgs = _check_images(images, len(cams), cams)
     return cams, imgs, _check_grid(grid)
-
-
-def _what(t):
-    return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-
-
-def _one_device(*tensors):
-    devices = sorted({str(t.device) for t in tensors})
-    if len(devices) != 1:
-        raise ValueError(f"the tensors of one call must be on one device, got {devices}")
-    _lib.require_device(*tensors)
-    return tensors[0].device
 
 
 # ---- the steps ----------------------------------------------------------------------------------------
@@ -136,8 +111,7 @@ def pick_plane(volume: torch.Tensor, views: torch.Tensor, alt_lo, step) -> dict:
     L = _sweep_lib.lib()
     volume, views = volume.contiguous(), views.contiguous()
     _, H, W = volume.shape
-    out = {"altitude": torch.empty((H, W), dtype=torch.float32, device=dev), "score": torch.empty((H, W), dtype=torch.float32, device=dev),
-           "index": torch.empty((H, W), dtype=torch.int32, device=dev), "views": torch.empty((H, W), dtype=torch.uint8, device=dev)}
+    out = _pick_planes(H, W, dev)
     _lib.check(L.spnerf_sweep_pick(_lib.ptr(volume), _lib.ptr(views), K, H * W, alt_lo, step, _lib.ptr(out["altitude"]),
                                    _lib.ptr(out["score"]), _lib.ptr(out["index"]), _lib.ptr(out["views"]), _lib.stream_of(volume)),
                "sweep_pick")
@@ -162,10 +136,7 @@ def plane_sweep(images, cameras, grid, alt_lo, step, planes, *, radius=2, min_vi
     V, (H, W), C = len(cams), grid.shape, imgs[0].shape[2]
     cam_table = _camera_table(cams, dev)
     img_table, imgs = _image_table(imgs, dev)
-    out = {"altitude": torch.empty((H, W), dtype=torch.float32, device=dev), "score": torch.empty((H, W), dtype=torch.float32, device=dev),
-           "index": torch.empty((H, W), dtype=torch.int32, device=dev), "views": torch.empty((H, W), dtype=torch.uint8, device=dev)}
-    if volume:
-        out["volume"] = torch.empty((K, H, W), dtype=torch.float32, device=dev)
+    out = _pick_planes(H, W, dev, K if volume else None)
     _lib.check(L.spnerf_sweep(ctypes.byref(_grid_struct(grid)), _lib.ptr(cam_table), _lib.ptr(img_table), V, C, alt_lo, step, K, radius,
                               min_views, min_std, _lib.ptr(out["altitude"]), _lib.ptr(out["score"]), _lib.ptr(out["index"]),
                               _lib.ptr(out["views"]), _lib.ptr(out.get("volume")), _lib.stream_of(out["altitude"])), "sweep")

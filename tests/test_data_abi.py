@@ -1,55 +1,36 @@
 """The training-set C ABI (include/spnerf_amd_data.h, spnerf_amd._data_lib) and the host side of
 spnerf_amd.dataset: the header, the ctypes table and the built library agree, argument errors
 come back as codes or ValueErrors before anything touches the GPU — no GPU needed."""
+import ctypes
 import os
-import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from spnerf_amd import _data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _view_lib
+import abi_util
+from spnerf_amd import _data_lib, _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_data.h")
+ROOT = abi_util.ROOT
+HEADER = abi_util.header_path("spnerf_amd_data.h")
 ONE = 256   # a non-NULL pointer value that is never dereferenced: the arguments are refused first
 
 
-def declarations():
-    """name → number of declared arguments, from the header text."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for name, args in re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
-        out[name] = 0 if args.strip() == "void" else len(args.split(","))
-    return out
-
-
 def test_data_exports_match_the_header():
-    decl = declarations()
-    assert sorted(decl) == ["spnerf_data_abi_version", "spnerf_depth_priors", "spnerf_rpc_rays_f64",
-                            "spnerf_scene_bounds", "spnerf_semantic_labels"]
-    L = _data_lib.lib()
-    assert L is _lib.lib()
-    for name in ("spnerf_depth_priors", "spnerf_scene_bounds", "spnerf_semantic_labels"):
-        assert hasattr(L, name), name
-    assert sorted(_data_lib.SIGNATURES) == sorted(decl), "data signature table out of sync with the header"
-    for name, n_args in decl.items():
-        assert hasattr(L, name), name
-        assert len(_data_lib.SIGNATURES[name][1]) == n_args, name
-    assert (decl["spnerf_depth_priors"], decl["spnerf_scene_bounds"], decl["spnerf_semantic_labels"]) == (20, 8, 12)
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib):
-        assert not set(_data_lib.SIGNATURES) & set(other.SIGNATURES)
-    hdr = open(HEADER).read()
-    consts = dict(re.findall(r"#define (SPNERF_DATA_[A-Z_]+) \(?(-?\d+)\)?", hdr))
-    assert L.spnerf_data_abi_version() == int(consts["SPNERF_DATA_ABI_VERSION"]) == _data_lib.SPNERF_DATA_ABI_VERSION
-    assert int(consts["SPNERF_DATA_WORKSPACE_BYTES"]) == _data_lib.DATA_WORKSPACE_BYTES
-    assert int(consts["SPNERF_DATA_VOID_LABEL"]) == _data_lib.VOID_LABEL == -100
-    assert L.spnerf_abi_version() == 2                      # the older ABIs are untouched
+    PD, PF = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float)
+    # the RPC coefficients, the scene centre and the offsets are host arrays
+    host = {("spnerf_rpc_rays_f64", 0): PD, ("spnerf_rpc_rays_f64", 6): PF, ("spnerf_rpc_rays_f64", 8): PF,
+            ("spnerf_depth_priors", 0): PD, ("spnerf_depth_priors", 5): PF, ("spnerf_scene_bounds", 0): PD}
+    assert abi_util.check_table(_data_lib, HEADER, "spnerf_", host) == [
+        "spnerf_data_abi_version", "spnerf_depth_priors", "spnerf_rpc_rays_f64", "spnerf_scene_bounds", "spnerf_semantic_labels"]
+    assert [len(_data_lib.SIGNATURES[n][1]) for n in ("spnerf_depth_priors", "spnerf_scene_bounds", "spnerf_semantic_labels")] == [20, 8, 12]
+    consts = abi_util.defines(HEADER, "SPNERF_DATA_")
+    assert consts["SPNERF_DATA_WORKSPACE_BYTES"] == _data_lib.DATA_WORKSPACE_BYTES
+    assert consts["SPNERF_DATA_VOID_LABEL"] == _data_lib.VOID_LABEL == -100
 
 
 def test_argument_errors_are_reported():
-    import ctypes
     L = _data_lib.lib()
     rpc = (ctypes.c_double * 90)()
     cen = (ctypes.c_float * 3)()

@@ -3,65 +3,24 @@ the ctypes table and the built library agree, the older ABIs are what they were,
 come back as codes before any launch, and the Trainer refuses a global batch that does not divide
 over the ranks before it touches the library or a device — no GPU needed."""
 import ctypes
-import os
 import re
 import types
 
 import pytest
 
-from spnerf_amd import _dp_lib, _eval_lib, _image_lib, _lib, _loss_lib, _train_lib, _view_lib, train
+import abi_util
+from spnerf_amd import _dp_lib, _train_lib, train
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_dp.h")
+HEADER = abi_util.header_path("spnerf_amd_dp.h")
 ONE = 256   # a non-NULL pointer value that is never dereferenced: the arguments are refused first
-
-C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
-
-
-def header_prototypes():
-    """{name: (return type, [argument type, ...])} of every function the header declares, pointers
-    reduced to ``*`` (or ``**`` for the host lists of device pointers)."""
-    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int32_t)\s+(spnerf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
-        types_ = []
-        for a in [x.strip() for x in args.split(",")]:
-            if a == "void":
-                continue
-            if "*" in a:
-                types_.append("**" if a.count("*") == 2 else "*")
-            else:
-                types_.append(a.split()[-2])
-        out[name] = (ret, types_)
-    return out
 
 
 def test_dp_exports_match_the_header():
-    protos = header_prototypes()
-    assert sorted(protos) == ["spnerf_adam_step_dev_scaled", "spnerf_dp_abi_version", "spnerf_dp_step_begin"]
-    L = _dp_lib.lib()
-    assert L is _lib.lib()
-    assert sorted(_dp_lib.SIGNATURES) == sorted(protos), "dp signature table out of sync with the header"
-    for name, (_, args) in protos.items():
-        assert hasattr(L, name), name
-        res, sig = _dp_lib.SIGNATURES[name]
-        assert res is ctypes.c_int32 and len(sig) == len(args), name
-        for i, (c, py) in enumerate(zip(args, sig)):
-            if c == "*":     # a device pointer, or the host array of element counts
-                assert py in (ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)), (name, i)
-            elif c == "**":  # a host array of device pointers
-                assert py is ctypes.POINTER(ctypes.c_void_p), (name, i)
-            else:
-                assert py is C_TYPES[c], (name, i, c)
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _train_lib):
-        assert not set(_dp_lib.SIGNATURES) & set(other.SIGNATURES)
+    # the element counts of the scaled Adam are a host array
+    names = abi_util.check_table(_dp_lib, HEADER, "spnerf_", {("spnerf_adam_step_dev_scaled", 5): ctypes.POINTER(ctypes.c_int64)})
+    assert names == ["spnerf_adam_step_dev_scaled", "spnerf_dp_abi_version", "spnerf_dp_step_begin"]
+    assert all(_dp_lib.SIGNATURES[n][0] is ctypes.c_int32 for n in names)
     txt = open(HEADER).read()
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_DP_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_dp_abi_version() == consts["SPNERF_DP_ABI_VERSION"] == _dp_lib.SPNERF_DP_ABI_VERSION == 1
-    # the older ABIs are untouched
-    _train_lib.lib()
-    assert L.spnerf_train_abi_version() == _train_lib.SPNERF_TRAIN_ABI_VERSION == 1
-    assert L.spnerf_abi_version() == 2 and L.spnerf_loss_abi_version() == 1
     # the scaled Adam takes spnerf_adam_step_dev's arguments with grad_scale before the stream
     a, b = _train_lib.SIGNATURES["spnerf_adam_step_dev"][1], _dp_lib.SIGNATURES["spnerf_adam_step_dev_scaled"][1]
     assert b[:-2] == a[:-1] and b[-2] is ctypes.c_float and b[-1] is a[-1]

@@ -2,59 +2,26 @@
 the built library agree, and argument errors come back as codes or are raised before any device is used — no
 GPU needed."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import (_dsmview_lib, _lib, _occlusion_lib, _ortho_lib, _rectify_lib, _sgm_lib, _shadow_lib, _surface_lib, _sweep_lib, dsm_view,
-                        rectify)
+from abi_util import A, B, C, D, refused
+from spnerf_amd import _dsmview_lib, _lib, _ortho_lib, dsm_view, rectify
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import load_cameras
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_dsmview.h")
-# non-NULL pointers far apart that are never dereferenced: the arguments are refused first
-A, B, C, D = (ctypes.c_void_p(k << 32) for k in (1, 2, 3, 4))
-C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
-           "const spnerf_ortho_grid*": ctypes.POINTER(_ortho_lib.OrthoGrid)}
+HEADER = abi_util.header_path("spnerf_amd_dsmview.h")
 
 
 def test_dsmview_exports_match_the_header():
-    txt = open(HEADER).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = {name: (res, args) for res, name, args in re.findall(r"(int32_t|int64_t) (spnerf_dsmview[a-z_]*)\(([^)]*)\);", code)}
-    assert sorted(protos) == ["spnerf_dsmview_abi_version", "spnerf_dsmview_cast", "spnerf_dsmview_ecef", "spnerf_dsmview_sample",
-                              "spnerf_dsmview_workspace_bytes"]
-    assert sorted(_dsmview_lib.SIGNATURES) == sorted(protos), "DSM-view signature table out of sync with the header"
-    L = _dsmview_lib.lib()
-    assert L is _lib.lib()
-    for name, (res, args) in protos.items():
-        assert hasattr(L, name), name
-        types = [] if args.strip() == "void" else [re.sub(r"\s*\w+$", "", " ".join(a.split())) for a in args.split(",")]
-        want = [C_TYPES.get(t, ctypes.c_void_p) for t in types]
-        for t in types:
-            assert t in C_TYPES or t.endswith("*"), (name, t)
-        got_res, got = _dsmview_lib.SIGNATURES[name]
-        assert got_res is C_TYPES[res] and got == want, name
-    for other in (_lib, _sweep_lib, _sgm_lib, _occlusion_lib, _surface_lib, _rectify_lib, _shadow_lib, _ortho_lib):
-        assert not set(_dsmview_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_DSMVIEW_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_dsmview_abi_version() == consts["SPNERF_DSMVIEW_ABI_VERSION"] == _dsmview_lib.SPNERF_DSMVIEW_ABI_VERSION == 1
+    assert abi_util.check_table(_dsmview_lib, HEADER, "spnerf_dsmview") == [
+        "spnerf_dsmview_abi_version", "spnerf_dsmview_cast", "spnerf_dsmview_ecef", "spnerf_dsmview_sample", "spnerf_dsmview_workspace_bytes"]
+    consts = abi_util.defines(HEADER, "SPNERF_DSMVIEW_")
     assert (consts["SPNERF_DSMVIEW_NEAREST"], consts["SPNERF_DSMVIEW_BILINEAR"]) == (_dsmview_lib.DSMVIEW_NEAREST, _dsmview_lib.DSMVIEW_BILINEAR) == (0, 1)
     assert dsm_view.MODES == {"nearest": 0, "bilinear": 1}
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2 and _sweep_lib.lib().spnerf_sweep_abi_version() == 1
-    assert _sgm_lib.lib().spnerf_sgm_abi_version() == 1 and _occlusion_lib.lib().spnerf_occlusion_abi_version() == 1
-    assert _surface_lib.lib().spnerf_surface_abi_version() == 1 and _rectify_lib.lib().spnerf_rectify_abi_version() == 1
-    assert _shadow_lib.lib().spnerf_shadow_abi_version() == 1
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
 
 
 def test_c_argument_errors_are_reported():

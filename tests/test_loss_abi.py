@@ -1,35 +1,21 @@
 """The training-loss C ABI (include/spnerf_amd_loss.h, spnerf_amd._loss_lib): the header, the ctypes
 table and the built library agree, and argument errors come back as codes — no GPU needed."""
 import ctypes
-import os
 import re
 
-from spnerf_amd import _eval_lib, _image_lib, _lib, _loss_lib, _view_lib
+import abi_util
+from spnerf_amd import _lib, _loss_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_loss.h")
+HEADER = abi_util.header_path("spnerf_amd_loss.h")
 ONE = 256   # a non-NULL pointer value that is never dereferenced: the arguments are refused first
 
 
-def header_symbols():
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_loss_exports_match_the_header():
-    syms = header_symbols()
-    assert syms == ["spnerf_loss_abi_version", "spnerf_train_loss_backward", "spnerf_train_loss_forward",
-                    "spnerf_train_loss_workspace_bytes"]
-    L = _loss_lib.lib()
-    assert L is _lib.lib()                                  # one library, five signature tables
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_loss_lib.SIGNATURES) == syms, "loss signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib):
-        assert not set(_loss_lib.SIGNATURES) & set(other.SIGNATURES)
-    hdr = open(HEADER).read()
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_LOSS_[A-Z0-9_]+) (\d+)\b", hdr)}
-    assert L.spnerf_loss_abi_version() == consts["SPNERF_LOSS_ABI_VERSION"] == _loss_lib.SPNERF_LOSS_ABI_VERSION == 1
+    structs = {"const spnerf_train_loss_opts*": ctypes.POINTER(_loss_lib.TrainLossOpts),
+               "const spnerf_train_loss_pass*": ctypes.POINTER(_loss_lib.TrainLossPass)}
+    assert abi_util.check_table(_loss_lib, HEADER, "spnerf_", structs) == [
+        "spnerf_loss_abi_version", "spnerf_train_loss_backward", "spnerf_train_loss_forward", "spnerf_train_loss_workspace_bytes"]
+    consts = abi_util.defines(HEADER, "SPNERF_LOSS_")
     assert consts["SPNERF_LOSS_BETA"] == _loss_lib.LOSS_BETA
     assert consts["SPNERF_LOSS_DEPTH_TERM_ONLY"] == _loss_lib.LOSS_DEPTH_TERM_ONLY
     assert consts["SPNERF_LOSS_SEM_TERM_ONLY"] == _loss_lib.LOSS_SEM_TERM_ONLY
@@ -42,7 +28,6 @@ def test_loss_exports_match_the_header():
     header_slots = {k[len("SPNERF_LOSS_TERM_"):].lower(): v for k, v in consts.items() if k.startswith("SPNERF_LOSS_TERM_")}
     ours = {k.replace("sc_term", "sc"): v for k, v in _loss_lib.TERM_SLOTS.items()}
     assert header_slots == ours
-    assert L.spnerf_abi_version() == 2                      # the older ABIs are untouched
 
 
 def test_loss_struct_layouts_match_the_header():

@@ -2,69 +2,39 @@
 table and the built library agree, and argument errors come back as codes or are raised before any
 device is used — no GPU needed."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import _lib, _occlusion_lib, _ortho_lib, _rectify_lib, _sgm_lib, _shadow_lib, _sweep_lib, occlusion, rectify
+from abi_util import ONE, grid_of, refused
+from spnerf_amd import _lib, _occlusion_lib, _shadow_lib, _sweep_lib, occlusion, rectify
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import load_cameras
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_occlusion.h")
-ONE = ctypes.c_void_p(256)   # non-NULL pointers that are never dereferenced: the arguments are refused first
-TWO = ctypes.c_void_p(512)
-C_TYPES = {"const spnerf_ortho_grid*": ctypes.POINTER(_ortho_lib.OrthoGrid), "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-           "double": ctypes.c_double, "const float* dirs": ctypes.POINTER(ctypes.c_float)}
-
-
-def grid_of(xsize=15, ysize=9, res=0.5, zone=17):
-    return ctypes.byref(_ortho_lib.OrthoGrid(438638.0, 3353655.0, res, xsize, ysize, zone, 0, 1))
+HEADER = abi_util.header_path("spnerf_amd_occlusion.h")
+TWO = ctypes.c_void_p(512)   # like ONE, a non-NULL pointer that is never dereferenced
 
 
 def test_occlusion_exports_match_the_header():
-    txt = open(HEADER).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = {name: (res, args) for res, name, args in re.findall(r"(int32_t|int64_t) (spnerf_occlusion[a-z_]*)\(([^)]*)\);", code)}
-    assert sorted(protos) == ["spnerf_occlusion_abi_version", "spnerf_occlusion_floor", "spnerf_occlusion_gate", "spnerf_occlusion_sweep",
-                              "spnerf_occlusion_workspace_bytes"]
-    assert sorted(_occlusion_lib.SIGNATURES) == sorted(protos), "occlusion signature table out of sync with the header"
+    # `dirs` is a host pointer to floats
+    assert abi_util.check_table(_occlusion_lib, HEADER, "spnerf_occlusion", {("spnerf_occlusion_floor", 4): ctypes.POINTER(ctypes.c_float)}) == [
+        "spnerf_occlusion_abi_version", "spnerf_occlusion_floor", "spnerf_occlusion_gate", "spnerf_occlusion_sweep", "spnerf_occlusion_workspace_bytes"]
     L = _occlusion_lib.lib()
-    assert L is _lib.lib()
-    for name, (res, args) in protos.items():
-        assert hasattr(L, name), name
-        params = [] if args.strip() == "void" else [" ".join(a.split()) for a in args.split(",")]
-        want = []
-        for p in params:
-            t = re.sub(r"\s*\w+$", "", p)
-            assert t in C_TYPES or t.endswith("*"), (name, t)
-            want.append(C_TYPES.get(p, C_TYPES.get(t, ctypes.c_void_p)))   # `dirs` is a host pointer to floats
-        got_res, got = _occlusion_lib.SIGNATURES[name]
-        assert got_res is C_TYPES[res] and got == want, name
-    for other in (_lib, _ortho_lib, _shadow_lib, _rectify_lib, _sweep_lib, _sgm_lib):
-        assert not set(_occlusion_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_OCCLUSION_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_occlusion_abi_version() == consts["SPNERF_OCCLUSION_ABI_VERSION"] == _occlusion_lib.SPNERF_OCCLUSION_ABI_VERSION == 1
+    txt = open(HEADER).read()
+    consts = abi_util.defines(HEADER, "SPNERF_OCCLUSION_")
     assert consts["SPNERF_OCCLUSION_MAX_VIEWS"] == _occlusion_lib.OCCLUSION_MAX_VIEWS == occlusion.MAX_VIEWS == _sweep_lib.SWEEP_MAX_VIEWS == 16
     # the march is stated in the words of the cast's header
-    cast = re.sub(r"\s*\*\s*", " ", open(os.path.join(ROOT, "include", "spnerf_amd_shadow.h")).read())
+    cast = re.sub(r"\s*\*\s*", " ", open(abi_util.header_path("spnerf_amd_shadow.h")).read())
     mine = re.sub(r"\s*\*\s*", " ", txt)
     for words in ("step m = 1, 2, ... visits column i' = i + m·sign(a) at row position y = j + m·q, q = b/|a|.",
                   "kept within [min(h0, h1), max(h0, h1)]; a step that needs a NaN height contributes nothing.",
                   "march ends when i' leaves the grid or y leaves [0, H - 1]."):
         assert words in cast and words in mine, words
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2 and _sweep_lib.lib().spnerf_sweep_abi_version() == 1 and _shadow_lib.lib().spnerf_shadow_abi_version() == 1
-    assert L.spnerf_occlusion_workspace_bytes(512, 512) == L.spnerf_shadow_workspace_bytes(512, 512) == 2048
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
+    assert L.spnerf_occlusion_workspace_bytes(512, 512) == _shadow_lib.lib().spnerf_shadow_workspace_bytes(512, 512) == 2048
 
 
 def test_c_argument_errors_are_reported():

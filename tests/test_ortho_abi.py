@@ -2,7 +2,6 @@
 table and the built library agree, and argument errors come back as codes or are raised before any
 device is used — no GPU needed."""
 import ctypes
-import os
 import re
 import types
 
@@ -10,31 +9,24 @@ import numpy as np
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import (_data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _ortho_lib, _relight_lib, _val_lib,
-                        _view_lib)
+from abi_util import ONE
+from spnerf_amd import _lib, _ortho_lib
 from spnerf_amd.ortho import GroundGrid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_ortho.h")
-ONE = ctypes.c_void_p(256)   # a non-NULL pointer that is never dereferenced: the arguments are refused first
+HEADER = abi_util.header_path("spnerf_amd_ortho.h")
 CENTER = (ctypes.c_double * 3)(801532.875, -5452266.5, 3200266.75)
 SUN = (ctypes.c_float * 3)(0.0, 0.6, 0.8)
 
 
 def test_ortho_exports_match_the_header():
+    # the scene centre and the sun direction are host arrays
+    host = {("spnerf_ortho_rays", 5): ctypes.POINTER(ctypes.c_double), ("spnerf_ortho_rays", 7): ctypes.POINTER(ctypes.c_float)}
+    assert abi_util.check_table(_ortho_lib, HEADER, "spnerf_", host) == [
+        "spnerf_ortho_abi_version", "spnerf_ortho_classes", "spnerf_ortho_rays", "spnerf_ortho_reduce"]
     txt = open(HEADER).read()
-    syms = sorted(set(re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == ["spnerf_ortho_abi_version", "spnerf_ortho_classes", "spnerf_ortho_rays", "spnerf_ortho_reduce"]
-    L = _ortho_lib.lib()
-    assert L is _lib.lib()                                  # one library, one more signature table
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_ortho_lib.SIGNATURES) == syms, "ortho signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _lpips_lib, _data_lib, _val_lib, _relight_lib):
-        assert not set(_ortho_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_ORTHO_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_ortho_abi_version() == consts["SPNERF_ORTHO_ABI_VERSION"] == _ortho_lib.SPNERF_ORTHO_ABI_VERSION == 1
+    consts = abi_util.defines(HEADER, "SPNERF_ORTHO_")
     assert consts["SPNERF_ORTHO_MAX_SUPERSAMPLE"] == _ortho_lib.ORTHO_MAX_SUPERSAMPLE == 4
     # the struct of the header, field for field
     body = re.search(r"typedef struct spnerf_ortho_grid \{(.*?)\} spnerf_ortho_grid;", txt, re.S).group(1)
@@ -42,11 +34,6 @@ def test_ortho_exports_match_the_header():
     fields = [n.split("[")[0] for decl in re.findall(r"(?:double|int32_t)\s+([^;]+);", body) for n in re.split(r",\s*", decl)]
     assert fields == [f for f, _ in _ortho_lib.OrthoGrid._fields_]
     assert ctypes.sizeof(_ortho_lib.OrthoGrid) == 3 * 8 + 8 * 4
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2
-    assert _relight_lib.lib().spnerf_relight_abi_version() == 1
-    assert _val_lib.lib().spnerf_val_abi_version() == 1
-    assert _view_lib.lib().spnerf_view_abi_version() == _view_lib.SPNERF_VIEW_ABI_VERSION
 
 
 def grid(xoff=438638.996411, ytop=3353655.999928, res=0.5, xsize=5, ysize=3, zone=17, south=0, s=1):

@@ -2,44 +2,29 @@
 ctypes table and the built library agree, and argument errors come back as codes or are raised before
 any device is used — no GPU needed."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import (_data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _ortho_lib, _rectify_lib, _relight_lib,
-                        _shadow_lib, _val_lib, _view_lib, rectify)
+from abi_util import ONE, grid_of, refused
+from spnerf_amd import _lib, _ortho_lib, _rectify_lib, rectify
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import RPCModel, load_cameras, rescale_rpc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_rectify.h")
-ONE = ctypes.c_void_p(256)   # non-NULL pointers that are never dereferenced: the arguments are refused first
-TWO = ctypes.c_void_p(512)
-
-
-def grid_of(xsize=15, ysize=9, res=0.5, zone=17, xoff=438638.0, ytop=3353655.0):
-    return ctypes.byref(_ortho_lib.OrthoGrid(xoff, ytop, res, xsize, ysize, zone, 0, 1))
+HEADER = abi_util.header_path("spnerf_amd_rectify.h")
+TWO = ctypes.c_void_p(512)   # like ONE, a non-NULL pointer that is never dereferenced
 
 
 def test_rectify_exports_match_the_header():
+    assert abi_util.check_table(_rectify_lib, HEADER, "spnerf_rectify") == [
+        "spnerf_rectify", "spnerf_rectify_abi_version", "spnerf_rectify_mosaic", "spnerf_rectify_project", "spnerf_rectify_sample",
+        "spnerf_rectify_view_dirs"]
     txt = open(HEADER).read()
-    syms = sorted(set(re.findall(r"\b(spnerf_rectify[a-z0-9_]*)\s*\(", txt)))
-    assert syms == ["spnerf_rectify", "spnerf_rectify_abi_version", "spnerf_rectify_mosaic", "spnerf_rectify_project",
-                    "spnerf_rectify_sample", "spnerf_rectify_view_dirs"]
-    L = _rectify_lib.lib()
-    assert L is _lib.lib()                                  # one library, one more signature table
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_rectify_lib.SIGNATURES) == syms, "rectify signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _lpips_lib, _data_lib, _val_lib, _relight_lib, _ortho_lib,
-                  _shadow_lib):
-        assert not set(_rectify_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_RECTIFY_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_rectify_abi_version() == consts["SPNERF_RECTIFY_ABI_VERSION"] == _rectify_lib.SPNERF_RECTIFY_ABI_VERSION == 1
+    consts = abi_util.defines(HEADER, "SPNERF_RECTIFY_")
     assert consts["SPNERF_RECTIFY_MAX_VIEWS"] == _rectify_lib.RECTIFY_MAX_VIEWS == rectify.MAX_VIEWS == 64
     assert consts["SPNERF_RECTIFY_MAX_CHANNELS"] == _rectify_lib.RECTIFY_MAX_CHANNELS == 4
     assert consts["SPNERF_RECTIFY_CAMERA_DOUBLES"] == _rectify_lib.RECTIFY_CAMERA_DOUBLES == 90
@@ -49,23 +34,12 @@ def test_rectify_exports_match_the_header():
     fields = [n.strip("* ") for decl in re.findall(r"(?:const float\*|int32_t)\s+([^;]+);", body) for n in re.split(r",\s*", decl)]
     assert fields == [f for f, _ in _rectify_lib.RectifyImage._fields_]
     assert ctypes.sizeof(_rectify_lib.RectifyImage) == _rectify_lib.IMAGE_BYTES == 16
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2
-    assert _ortho_lib.lib().spnerf_ortho_abi_version() == 1
-    assert _relight_lib.lib().spnerf_relight_abi_version() == 1
-    assert _shadow_lib.lib().spnerf_shadow_abi_version() == 1
-    assert _view_lib.lib().spnerf_view_abi_version() == _view_lib.SPNERF_VIEW_ABI_VERSION
 
 
 GRID_ERRORS = ((dict(xsize=0), b"grid of 0 x 9"), (dict(ysize=-3), b"grid of 15 x -3"),
                (dict(xsize=2 ** 31 - 1, ysize=2 ** 31 - 1), b"too large"), (dict(zone=0), b"UTM zone 0"), (dict(zone=61), b"UTM zone 61"),
                (dict(res=0.0), b"resolution 0"), (dict(res=float("nan")), b"resolution"), (dict(res=float("inf")), b"resolution"),
                (dict(xoff=float("nan")), b"non-finite grid origin"), (dict(ytop=float("inf")), b"non-finite grid origin"))
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
 
 
 def test_project_and_fused_argument_errors_are_reported():
@@ -151,8 +125,9 @@ def test_python_argument_errors_come_before_any_device_use():
                 call(dsm=bad)
         with pytest.raises(ValueError, match="is not the grid's"):
             call(grid=GroundGrid(438638.0, 3353655.0, 9, 15, 0.5, 17))               # 15 rows of 9 cells, not 9 of 15
-        with pytest.raises(ValueError, match="grid must be a GroundGrid"):
-            call(grid=0.5)
+        for bad in (0.5, None):
+            with pytest.raises(ValueError, match="grid must be a GroundGrid"):
+                call(grid=bad)
         with pytest.raises(ValueError, match="cameras in one call"):
             call(cams=[], images=[])
         with pytest.raises(ValueError, match="65 cameras in one call"):

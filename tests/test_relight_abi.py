@@ -2,7 +2,6 @@
 ctypes table and the built library agree, and argument errors come back as codes or are raised
 before any device is used — no GPU needed."""
 import ctypes
-import os
 import re
 import types
 
@@ -10,12 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import _data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _relight_lib, _val_lib, _view_lib
+from abi_util import ONE
+from spnerf_amd import _lib, _relight_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_relight.h")
-ONE = ctypes.c_void_p(256)   # a non-NULL pointer that is never dereferenced: the arguments are refused first
+HEADER = abi_util.header_path("spnerf_amd_relight.h")
 
 
 def cfg(width=64, dtype=1):
@@ -25,23 +24,11 @@ def cfg(width=64, dtype=1):
 
 
 def test_relight_exports_match_the_header():
-    txt = open(HEADER).read()
-    syms = sorted(set(re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == ["spnerf_relight_abi_version", "spnerf_relight_composite", "spnerf_relight_directions",
-                    "spnerf_relight_sun", "spnerf_relight_workspace_bytes"]
-    L = _relight_lib.lib()
-    assert L is _lib.lib()                                  # one library, one more signature table
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_relight_lib.SIGNATURES) == syms, "relight signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _lpips_lib, _data_lib, _val_lib):
-        assert not set(_relight_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_RELIGHT_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_relight_abi_version() == consts["SPNERF_RELIGHT_ABI_VERSION"] == _relight_lib.SPNERF_RELIGHT_ABI_VERSION == 1
-    # the older ABIs are untouched; the new MLP flag is the header's
-    assert L.spnerf_abi_version() == 2
-    assert _val_lib.lib().spnerf_val_abi_version() == 1
-    main = open(os.path.join(ROOT, "include", "spnerf_amd.h")).read()
+    assert abi_util.check_table(_relight_lib, HEADER, "spnerf_") == [
+        "spnerf_relight_abi_version", "spnerf_relight_composite", "spnerf_relight_directions", "spnerf_relight_sun",
+        "spnerf_relight_workspace_bytes"]
+    # the new MLP flag is the header's
+    main = open(abi_util.header_path("spnerf_amd.h")).read()
     assert int(re.search(r"#define SPNERF_MLP_KEEP_FEAT (\d+)\b", main).group(1)) == _lib.SPNERF_MLP_KEEP_FEAT == 32
 
 

@@ -2,59 +2,29 @@
 ctypes table and the built library agree, and argument errors come back as codes or are raised before
 any device is used — no GPU needed."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import (_data_lib, _dp_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _ortho_lib, _rectify_lib, _relight_lib,
-                        _sgm_lib, _shadow_lib, _sweep_lib, _train_lib, _val_lib, _view_lib, rectify, sgm)
+from abi_util import A as VOL, B as OUT, C as WORK, D as FOUR, refused
+from spnerf_amd import _lib, _sgm_lib, rectify, sgm
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import load_cameras
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_sgm.h")
-# non-NULL pointers far apart that are never dereferenced: the arguments are refused first
-VOL, OUT, WORK, FOUR = (ctypes.c_void_p(k << 32) for k in (1, 2, 3, 4))
-C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
-           "int64_t*": ctypes.POINTER(ctypes.c_int64)}
-OTHERS = (_lib, _data_lib, _dp_lib, _eval_lib, _image_lib, _loss_lib, _lpips_lib, _ortho_lib, _rectify_lib, _relight_lib, _shadow_lib,
-          _sweep_lib, _train_lib, _val_lib, _view_lib)
+HEADER = abi_util.header_path("spnerf_amd_sgm.h")
 
 
 def test_sgm_exports_match_the_header():
+    names = abi_util.check_table(_sgm_lib, HEADER, "spnerf_sgm", {"int64_t*": ctypes.POINTER(ctypes.c_int64)})
+    assert names == ["spnerf_sgm_abi_version", "spnerf_sgm_aggregate", "spnerf_sgm_pick", "spnerf_sgm_workspace_bytes"]
+    assert all(_sgm_lib.SIGNATURES[n][0] is ctypes.c_int32 for n in names)
     txt = open(HEADER).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = dict(re.findall(r"int32_t (spnerf_sgm[a-z_]*)\(([^)]*)\);", code))
-    assert sorted(protos) == ["spnerf_sgm_abi_version", "spnerf_sgm_aggregate", "spnerf_sgm_pick", "spnerf_sgm_workspace_bytes"]
-    assert sorted(_sgm_lib.SIGNATURES) == sorted(protos), "sgm signature table out of sync with the header"
-    L = _sgm_lib.lib()
-    assert L is _lib.lib()
-    for name, args in protos.items():
-        assert hasattr(L, name), name
-        types = [] if args.strip() == "void" else [re.sub(r"\s*\w+$", "", " ".join(a.split())) for a in args.split(",")]
-        want = [C_TYPES.get(t, ctypes.c_void_p) for t in types]
-        for t in types:
-            assert t in C_TYPES or t.endswith("*"), (name, t)
-        res, got = _sgm_lib.SIGNATURES[name]
-        assert res is ctypes.c_int32 and got == want, name
-    for other in OTHERS:
-        assert not set(_sgm_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_SGM_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_sgm_abi_version() == consts["SPNERF_SGM_ABI_VERSION"] == _sgm_lib.SPNERF_SGM_ABI_VERSION == 1
+    consts = abi_util.defines(HEADER, "SPNERF_SGM_")
     assert consts["SPNERF_SGM_MAX_PLANES"] == _sgm_lib.SGM_MAX_PLANES == sgm.MAX_PLANES == 512
     assert consts["SPNERF_SGM_TILE"] == _sgm_lib.SGM_TILE == 64
     assert "There is no `views` output" in txt and "Occlusion is not modelled" in txt
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2 and _rectify_lib.lib().spnerf_rectify_abi_version() == 1
-    assert _sweep_lib.lib().spnerf_sweep_abi_version() == 1
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
 
 
 SIZE_ERRORS = ((dict(K=0), b"n_planes 0 outside [1, 512]"), (dict(K=513), b"n_planes 513 outside [1, 512]"), (dict(H=0), b"grid of 15 x 0"),

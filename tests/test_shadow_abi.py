@@ -2,7 +2,6 @@
 ctypes table and the built library agree, and argument errors come back as codes or are raised before
 any device is used — no GPU needed."""
 import ctypes
-import os
 import re
 import types
 
@@ -10,15 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import (_data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _ortho_lib, _relight_lib, _shadow_lib,
-                        _val_lib, _view_lib)
+from abi_util import ONE
+from spnerf_amd import _lib, _shadow_lib
 from spnerf_amd.ortho import GroundGrid
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_shadow.h")
-ONE = ctypes.c_void_p(256)   # a non-NULL, 16-byte aligned pointer that is never dereferenced: the arguments are refused first
-TWO = ctypes.c_void_p(512)
+HEADER = abi_util.header_path("spnerf_amd_shadow.h")
+TWO = ctypes.c_void_p(512)   # like ONE, a non-NULL, 16-byte aligned pointer that is never dereferenced
 
 
 def dirs_of(*rows):
@@ -26,19 +24,12 @@ def dirs_of(*rows):
 
 
 def test_shadow_exports_match_the_header():
+    # `dirs` is a host pointer to floats
+    assert abi_util.check_table(_shadow_lib, HEADER, "spnerf_", {("spnerf_shadow_cast", 4): ctypes.POINTER(ctypes.c_float)}) == [
+        "spnerf_shadow_abi_version", "spnerf_shadow_agreement", "spnerf_shadow_agreement_workspace_bytes", "spnerf_shadow_cast",
+        "spnerf_shadow_workspace_bytes"]
     txt = open(HEADER).read()
-    syms = sorted(set(re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(", txt)))
-    assert syms == ["spnerf_shadow_abi_version", "spnerf_shadow_agreement", "spnerf_shadow_agreement_workspace_bytes",
-                    "spnerf_shadow_cast", "spnerf_shadow_workspace_bytes"]
-    L = _shadow_lib.lib()
-    assert L is _lib.lib()                                  # one library, one more signature table
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_shadow_lib.SIGNATURES) == syms, "shadow signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _lpips_lib, _data_lib, _val_lib, _relight_lib, _ortho_lib):
-        assert not set(_shadow_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_SHADOW_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_shadow_abi_version() == consts["SPNERF_SHADOW_ABI_VERSION"] == _shadow_lib.SPNERF_SHADOW_ABI_VERSION == 1
+    consts = abi_util.defines(HEADER, "SPNERF_SHADOW_")
     assert consts["SPNERF_SHADOW_MAX_DIRS"] == _shadow_lib.SHADOW_MAX_DIRS == 65535
     # the struct of the header, field for field
     body = re.search(r"typedef struct spnerf_shadow_agreement_result \{(.*?)\} spnerf_shadow_agreement_result;", txt, re.S).group(1)
@@ -46,11 +37,6 @@ def test_shadow_exports_match_the_header():
     fields = [n for decl in re.findall(r"(?:double|int64_t)\s+([^;]+);", body) for n in re.split(r",\s*", decl)]
     assert fields == [f for f, _ in _shadow_lib.ShadowAgreementResult._fields_]
     assert ctypes.sizeof(_shadow_lib.ShadowAgreementResult) == _shadow_lib.RESULT_BYTES == 8 * 8
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2
-    assert _ortho_lib.lib().spnerf_ortho_abi_version() == 1
-    assert _relight_lib.lib().spnerf_relight_abi_version() == 1
-    assert _view_lib.lib().spnerf_view_abi_version() == _view_lib.SPNERF_VIEW_ABI_VERSION
 
 
 def test_workspace_sizes():

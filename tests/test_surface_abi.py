@@ -2,55 +2,26 @@
 table and the built library agree, and argument errors come back as codes or are raised before any device is
 used — no GPU needed."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import _lib, _occlusion_lib, _ortho_lib, _sgm_lib, _surface_lib, _sweep_lib, rectify, sgm, surface
+from abi_util import A, B, C, D, refused
+from spnerf_amd import _lib, _ortho_lib, _surface_lib, rectify, sgm, surface
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import load_cameras
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_surface.h")
-# non-NULL pointers far apart that are never dereferenced: the arguments are refused first
-A, B, C, D = (ctypes.c_void_p(k << 32) for k in (1, 2, 3, 4))
-C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
-           "const spnerf_ortho_grid*": ctypes.POINTER(_ortho_lib.OrthoGrid)}
+HEADER = abi_util.header_path("spnerf_amd_surface.h")
 
 
 def test_surface_exports_match_the_header():
-    txt = open(HEADER).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = dict(re.findall(r"int32_t (spnerf_surface[a-z_]*)\(([^)]*)\);", code))
-    assert sorted(protos) == ["spnerf_surface_abi_version", "spnerf_surface_grey", "spnerf_surface_lift", "spnerf_surface_sweep",
-                              "spnerf_surface_upsample"]
-    assert sorted(_surface_lib.SIGNATURES) == sorted(protos), "surface signature table out of sync with the header"
-    L = _surface_lib.lib()
-    assert L is _lib.lib()
-    for name, args in protos.items():
-        assert hasattr(L, name), name
-        types = [] if args.strip() == "void" else [re.sub(r"\s*\w+$", "", " ".join(a.split())) for a in args.split(",")]
-        want = [C_TYPES.get(t, ctypes.c_void_p) for t in types]
-        for t in types:
-            assert t in C_TYPES or t.endswith("*"), (name, t)
-        res, got = _surface_lib.SIGNATURES[name]
-        assert res is ctypes.c_int32 and got == want, name
-    for other in (_lib, _sweep_lib, _sgm_lib, _occlusion_lib):
-        assert not set(_surface_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_SURFACE_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_surface_abi_version() == consts["SPNERF_SURFACE_ABI_VERSION"] == _surface_lib.SPNERF_SURFACE_ABI_VERSION == 1
+    names = abi_util.check_table(_surface_lib, HEADER, "spnerf_surface")
+    assert names == ["spnerf_surface_abi_version", "spnerf_surface_grey", "spnerf_surface_lift", "spnerf_surface_sweep", "spnerf_surface_upsample"]
+    assert all(_surface_lib.SIGNATURES[n][0] is ctypes.c_int32 for n in names)
+    consts = abi_util.defines(HEADER, "SPNERF_SURFACE_")
     assert consts["SPNERF_SURFACE_MAX_FACTOR"] == _surface_lib.SURFACE_MAX_FACTOR == surface.MAX_FACTOR == 8
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2 and _sweep_lib.lib().spnerf_sweep_abi_version() == 1
-    assert _sgm_lib.lib().spnerf_sgm_abi_version() == 1 and _occlusion_lib.lib().spnerf_occlusion_abi_version() == 1
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
 
 
 def test_c_argument_errors_are_reported():

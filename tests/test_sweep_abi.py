@@ -2,62 +2,33 @@
 table and the built library agree, and argument errors come back as codes or are raised before any
 device is used — no GPU needed."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import abi_util
 import spnerf_amd
-from spnerf_amd import _lib, _ortho_lib, _rectify_lib, _shadow_lib, _sweep_lib, rectify, sweep
+from abi_util import ONE, grid_of, refused
+from spnerf_amd import _lib, _sweep_lib, rectify, sweep
 from spnerf_amd.ortho import GroundGrid
 from spnerf_amd.satellite import load_cameras
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_sweep.h")
-ONE = ctypes.c_void_p(256)   # non-NULL pointers that are never dereferenced: the arguments are refused first
-TWO = ctypes.c_void_p(512)
-C_TYPES = {"const spnerf_ortho_grid*": ctypes.POINTER(_ortho_lib.OrthoGrid), "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-           "double": ctypes.c_double}
-
-
-def grid_of(xsize=15, ysize=9, res=0.5, zone=17):
-    return ctypes.byref(_ortho_lib.OrthoGrid(438638.0, 3353655.0, res, xsize, ysize, zone, 0, 1))
+HEADER = abi_util.header_path("spnerf_amd_sweep.h")
+TWO = ctypes.c_void_p(512)   # like ONE, a non-NULL pointer that is never dereferenced
 
 
 def test_sweep_exports_match_the_header():
+    names = abi_util.check_table(_sweep_lib, HEADER, "spnerf_sweep")
+    assert names == ["spnerf_sweep", "spnerf_sweep_abi_version", "spnerf_sweep_grey", "spnerf_sweep_pick", "spnerf_sweep_score"]
+    assert all(_sweep_lib.SIGNATURES[n][0] is ctypes.c_int32 for n in names)
     txt = open(HEADER).read()
-    code = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = dict(re.findall(r"int32_t (spnerf_sweep[a-z_]*)\(([^)]*)\);", code))
-    assert sorted(protos) == ["spnerf_sweep", "spnerf_sweep_abi_version", "spnerf_sweep_grey", "spnerf_sweep_pick", "spnerf_sweep_score"]
-    assert sorted(_sweep_lib.SIGNATURES) == sorted(protos), "sweep signature table out of sync with the header"
-    L = _sweep_lib.lib()
-    assert L is _lib.lib()
-    for name, args in protos.items():
-        assert hasattr(L, name), name
-        types = [] if args.strip() == "void" else [re.sub(r"\s*\w+$", "", " ".join(a.split())) for a in args.split(",")]
-        want = [C_TYPES.get(t, ctypes.c_void_p) for t in types]
-        for t in types:
-            assert t in C_TYPES or t.endswith("*"), (name, t)
-        res, got = _sweep_lib.SIGNATURES[name]
-        assert res is ctypes.c_int32 and got == want, name
-    for other in (_lib, _ortho_lib, _shadow_lib, _rectify_lib):
-        assert not set(_sweep_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_SWEEP_[A-Z0-9_]+) (\d+)\b", txt)}
-    assert L.spnerf_sweep_abi_version() == consts["SPNERF_SWEEP_ABI_VERSION"] == _sweep_lib.SPNERF_SWEEP_ABI_VERSION == 1
+    consts = abi_util.defines(HEADER, "SPNERF_SWEEP_")
     assert consts["SPNERF_SWEEP_MIN_VIEWS"] == _sweep_lib.SWEEP_MIN_VIEWS == sweep.MIN_VIEWS == 2
     assert consts["SPNERF_SWEEP_MAX_VIEWS"] == _sweep_lib.SWEEP_MAX_VIEWS == sweep.MAX_VIEWS == 16
     assert consts["SPNERF_SWEEP_MAX_PLANES"] == _sweep_lib.SWEEP_MAX_PLANES == sweep.MAX_PLANES == 4096
     assert consts["SPNERF_SWEEP_MAX_RADIUS"] == _sweep_lib.SWEEP_MAX_RADIUS == sweep.MAX_RADIUS == 4
     assert consts["SPNERF_SWEEP_TILE"] == _sweep_lib.SWEEP_TILE == 16
     assert "Occlusion is not modelled" in txt
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2 and _rectify_lib.lib().spnerf_rectify_abi_version() == 1
-
-
-def refused(L, rc, text, what):
-    assert rc == _lib.SPNERF_E_ARG == -1, what
-    assert text in L.spnerf_last_error(), (what, L.spnerf_last_error())
 
 
 VIEW_ERRORS = ((dict(v=1), b"n_views 1 outside [2, 16]"), (dict(v=17), b"n_views 17 outside [2, 16]"), (dict(v=0), b"n_views 0"))

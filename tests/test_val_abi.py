@@ -1,41 +1,20 @@
 """The validation-loss C ABI (include/spnerf_amd_val.h, spnerf_amd._val_lib): the header, the ctypes
 table and the built library agree, and argument errors come back as codes — no GPU needed."""
 import ctypes
-import os
 import re
 
 import pytest
 
-from spnerf_amd import _data_lib, _eval_lib, _image_lib, _lib, _loss_lib, _lpips_lib, _val_lib, _view_lib
+import abi_util
+from abi_util import ONE
+from spnerf_amd import _lib, _val_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "spnerf_amd_val.h")
-ONE = ctypes.c_void_p(256)   # a non-NULL pointer that is never dereferenced: the arguments are refused first
-
-
-def header_symbols():
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"\b(spnerf_[a-z0-9_]+)\s*\(", txt)))
+HEADER = abi_util.header_path("spnerf_amd_val.h")
 
 
 def test_val_exports_match_the_header():
-    syms = header_symbols()
-    assert syms == ["spnerf_val_abi_version", "spnerf_val_loss", "spnerf_val_loss_workspace_bytes", "spnerf_val_solar_terms"]
-    L = _val_lib.lib()
-    assert L is _lib.lib()                                  # one library, one more signature table
-    for s in syms:
-        assert hasattr(L, s), s
-    assert sorted(_val_lib.SIGNATURES) == syms, "val signature table out of sync with the header"
-    for other in (_lib, _eval_lib, _view_lib, _image_lib, _loss_lib, _lpips_lib, _data_lib):
-        assert not set(_val_lib.SIGNATURES) & set(other.SIGNATURES), other.__name__
-    hdr = open(HEADER).read()
-    consts = {k: int(v) for k, v in re.findall(r"#define (SPNERF_VAL_[A-Z0-9_]+) (\d+)\b", hdr)}
-    assert L.spnerf_val_abi_version() == consts["SPNERF_VAL_ABI_VERSION"] == _val_lib.SPNERF_VAL_ABI_VERSION == 1
-    # the older ABIs are untouched
-    assert L.spnerf_abi_version() == 2
-    assert L.spnerf_eval_abi_version() == 1
-    assert _view_lib.lib().spnerf_view_abi_version() == _view_lib.SPNERF_VIEW_ABI_VERSION == 1
-    assert _loss_lib.lib().spnerf_loss_abi_version() == _loss_lib.SPNERF_LOSS_ABI_VERSION == 1
+    assert abi_util.check_table(_val_lib, HEADER, "spnerf_") == [
+        "spnerf_val_abi_version", "spnerf_val_loss", "spnerf_val_loss_workspace_bytes", "spnerf_val_solar_terms"]
 
 
 def test_val_result_layout_matches_the_header():

@@ -38,6 +38,8 @@ from . import surface  # noqa: F401  (the sweep around a base surface instead of
 from .surface import coarsen, pyramid_sweep, surface_grey, surface_lift, surface_sweep, upsample_dsm  # noqa: F401
 from . import dsm_view  # noqa: F401  (a ground-grid DSM seen from a camera: the cast, rasters read at the hits, depth priors)
 from .dsm_view import dsm_depth_priors, hit_ecef, normalised_depth, sample_at, view_dsm  # noqa: F401
+from . import clean  # noqa: F401  (a swept DSM cleaned: the speckle filter, the median, the hole fill, and the two-pass sweep over a cleaned prior)
+from .clean import bootstrap_sweep, clean_dsm, fill_holes, median_dsm, speckle_filter  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

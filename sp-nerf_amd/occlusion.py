@@ -145,7 +145,9 @@ def refine_sweep(images, cameras, grid, alt_lo, step, planes, *, prior=None, sla
     floor was made from), and with ``volume=True`` also ``volume`` and ``aggregated``.  The aggregation
     itself does not know the gate.  The floor is a maximum along the line of sight, so the result is as good
     as the prior: on the JAX_269 ROI the lidar as the prior improves on ``smooth_sweep``, the sweep's own noisy
-    first pass makes it worse."""
+    first pass makes it worse.  Without a lidar use ``clean.bootstrap_sweep``, which takes the
+    speckles out of the first pass before the floor is made from it: that brings the error back to
+    ``smooth_sweep``'s, not below it."""
     cams, imgs, grid = _sweep._check_scene(images, cameras, grid)
     alt_lo, step, K = _sweep._check_planes(alt_lo, step, planes)
     _check_int("planes", K, 2, sgm.MAX_PLANES)

@@ -40,6 +40,8 @@ from . import dsm_view  # noqa: F401  (a ground-grid DSM seen from a camera: the
 from .dsm_view import dsm_depth_priors, hit_ecef, normalised_depth, sample_at, view_dsm  # noqa: F401
 from . import clean  # noqa: F401  (a swept DSM cleaned: the speckle filter, the median, the hole fill, and the two-pass sweep over a cleaned prior)
 from .clean import bootstrap_sweep, clean_dsm, fill_holes, median_dsm, speckle_filter  # noqa: F401
+from . import confidence  # noqa: F401  (how unambiguous a pick is, from the score volume: margins, peak counts, curvature, the maximum-likelihood measure)
+from .confidence import sparsification, volume_confidence  # noqa: F401
 from . import image  # noqa: F401  (image scores: the reference's metrics.ssim in fp64 on the GPU)
 from .image import ssim  # noqa: F401
 from . import perceptual  # noqa: F401  (LPIPS with AlexNet features: eval.py:128-135 on the GPU)

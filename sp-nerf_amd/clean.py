@@ -12,8 +12,7 @@ raster is an (H, W) float32 device tensor, row 0 the northernmost; a cell that i
 are never written.  The header states every operation: nothing rounds, and the results are the bytes of the
 numpy statement (tests/clean_numpy.py).
 
-Not there: a confidence from the score volume (the margin between the best and the second-best plane),
-occlusion-aware aggregation, and an edge-aware fill guided by the ortho mosaic.
+Not there: occlusion-aware aggregation, and an edge-aware fill guided by the ortho mosaic.
 """
 from __future__ import annotations
 
@@ -39,6 +38,9 @@ SPECKLE_CELLS = 100
 MAX_DIFF_STEPS = 2
 MEDIAN_RADIUS = 0
 MIN_WEIGHT = 0.25
+# what bootstrap_sweep's prior may be gated on: the first pass's raw ZNCC at the pick, or a plane volume_confidence
+# takes from the first pass's aggregated volume
+WEIGHTS = ("photo", "margin", "peak_margin", "curvature", "mlm")
 
 
 # ---- argument checks: everything below is decided on the host, before any device is touched ------
@@ -196,14 +198,17 @@ def clean_dsm(dsm: torch.Tensor, *, weight=None, min_weight=None, max_diff, max_
 
 def bootstrap_sweep(images, cameras, grid, alt_lo, step, planes, *, max_diff=None, max_size=None, radius=MEDIAN_RADIUS, min_weight=MIN_WEIGHT,
                     reach=None, mode="lowest", min_dirs=1, slack=None, sweep_radius=2, min_views=2, min_std=0.0, p1=sgm.P1, p2=sgm.P2, unscored=1.0,
-                    paths=8, volume=False) -> dict:
+                    paths=8, volume=False, weight="photo") -> dict:
     """``refine_sweep`` from its own first pass with the outliers taken out of the prior: ``smooth_sweep``, then
     ``clean_dsm`` of its ``altitude`` (with its ``photo``, the raw ZNCC at the pick, as the weight unless
     ``min_weight`` is None), then ``refine_sweep(prior=cleaned)``.  Returns ``refine_sweep``'s dict plus ``first``
     (the first pass's altitude) and ``cleaned`` (``clean_dsm``'s dict).  ``max_diff`` defaults to ``MAX_DIFF_STEPS``
     ``step``s, ``max_size`` to ``SPECKLE_CELLS``, ``slack`` to one ``step``; ``radius`` is the median's (0: none) and
     ``sweep_radius`` the ZNCC window's, ``refine_sweep``'s ``radius``.  With ``reach=None`` the cleaned prior keeps its
-    holes: the floor's march skips NaN, so a removed outlier hides nothing.  On the JAX_269 ROI this takes the two-pass
+    holes: the floor's march skips NaN, so a removed outlier hides nothing.  ``weight`` names what ``min_weight`` gates:
+    "photo", or one of "margin", "peak_margin", "curvature", "mlm" — that plane of ``volume_confidence`` over the first
+    pass's aggregated volume at its defaults (a NaN there, no second peak or no neighbour, is rejected like any NaN
+    weight); ``min_weight`` is then on that plane's scale and has no default worth keeping.  On the JAX_269 ROI this takes the two-pass
     sweep from 12.4 m back to ``smooth_sweep``'s 7.6 m of altitude MAE, not below it."""
     from . import occlusion
     cams, imgs, grid = _sweep._check_scene(images, cameras, grid)
@@ -222,10 +227,18 @@ def bootstrap_sweep(images, cameras, grid, alt_lo, step, planes, *, max_diff=Non
         raise ValueError(f"a grid of {grid.shape[1]} x {grid.shape[0]} cells is too large for one call")
     if min_weight is not None:
         _check_real("min_weight", min_weight, "finite", lambda x: True)
+    if not isinstance(weight, str) or weight not in WEIGHTS:
+        raise ValueError(f"weight {weight!r} must be one of {', '.join(map(repr, WEIGHTS))}")
     _one_device(*imgs)
     kw = dict(radius=sweep_radius, min_views=min_views, min_std=min_std, p1=p1, p2=p2, unscored=unscored, paths=paths)
-    first = sgm.smooth_sweep(images, cameras, grid, alt_lo, step, K, **kw)
-    cleaned = clean_dsm(first["altitude"], weight=None if min_weight is None else first["photo"], min_weight=min_weight, max_diff=max_diff,
+    if weight == "photo" or min_weight is None:
+        first = sgm.smooth_sweep(images, cameras, grid, alt_lo, step, K, **kw)
+        gate = first["photo"]
+    else:
+        from .confidence import volume_confidence
+        first = sgm.smooth_sweep(images, cameras, grid, alt_lo, step, K, volume=True, **kw)
+        gate = volume_confidence(first["aggregated"], alt_lo, step, planes=(weight,))[weight]
+    cleaned = clean_dsm(first["altitude"], weight=None if min_weight is None else gate, min_weight=min_weight, max_diff=max_diff,
                         max_size=max_size, radius=radius, reach=reach, mode=mode, min_dirs=min_dirs)
     out = occlusion.refine_sweep(images, cameras, grid, alt_lo, step, K, prior=cleaned["dsm"], slack=slack, volume=volume, **kw)
     out["first"], out["cleaned"] = first["altitude"], cleaned

@@ -106,12 +106,14 @@ def pick(aggregated: torch.Tensor, volume: torch.Tensor, alt_lo, step) -> dict:
 
 
 def smooth_sweep(images, cameras, grid, alt_lo, step, planes, *, radius=2, min_views=2, min_std=0.0, p1=P1, p2=P2, unscored=1.0,
-                 paths=8, volume=False) -> dict:
+                 paths=8, volume=False, confidence=False) -> dict:
     """``plane_sweep(volume=True)`` → ``aggregate`` → ``pick``: the swept DSM with its planes chosen
     jointly across cells.  Returns a dict of (H, W) device tensors — ``altitude``, ``score`` (the
     aggregated value), ``index`` and ``photo`` (the raw ZNCC at the chosen plane) — and with
     ``volume=True`` also ``volume`` and ``aggregated`` (K, H, W).  ``altitude`` feeds ``orthorectify`` and
-    ``cast_shadows`` as the sweep's does."""
+    ``cast_shadows`` as the sweep's does.  With ``confidence=True`` also ``confidence``, the dict
+    ``volume_confidence`` gives for the aggregated volume at its defaults, and ``confidence_raw``, the same
+    for the raw one; every other plane is what it is without."""
     cams, _, _ = _sweep._check_scene(images, cameras, grid)
     _sweep._check_planes(alt_lo, step, planes)
     _check_int("planes", planes, 1, MAX_PLANES)
@@ -119,10 +121,15 @@ def smooth_sweep(images, cameras, grid, alt_lo, step, planes, *, radius=2, min_v
     _check_penalties(p1, p2, unscored, paths)
     if not isinstance(volume, bool):
         raise ValueError(f"volume {volume!r} must be a bool")
+    if not isinstance(confidence, bool):
+        raise ValueError(f"confidence {confidence!r} must be a bool")
     raw = _sweep.plane_sweep(images, cameras, grid, alt_lo, step, planes, radius=radius, min_views=min_views, min_std=min_std,
                              volume=True)["volume"]
     agg = aggregate(raw, p1=p1, p2=p2, unscored=unscored, paths=paths)
     out = pick(agg, raw, alt_lo, step)
     if volume:
         out["volume"], out["aggregated"] = raw, agg
+    if confidence:
+        from .confidence import volume_confidence
+        out["confidence"], out["confidence_raw"] = volume_confidence(agg, alt_lo, step), volume_confidence(raw, alt_lo, step)
     return out
